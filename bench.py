@@ -2,7 +2,18 @@
 """Benchmark of the decoding hot path (contract: see README / DESIGN.md "Measurement").
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload minsum-z32|...]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line (throughput, ms_per_step,
+the last step's BER / FER counters, the kernel time and its algorithmic roofline arithmetic).
+`--full` adds what needs work or measurements of its own: the CPU baseline (the oracle on a sample of
+--cpu-baseline-seconds) and the PMC-based roofline figures (VALU instruction rate, measured HBM
+traffic) looked up in profiles/ and checked against the loaded library's build.
+`--dump-outputs DIR` writes what the last timed step computed (the arrays its caller receives) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output (the
+inference workloads repeat bit for bit; a training step's backward accumulates with atomics, so
+gnn-train-* repeats to float32 rounding).
 
 `--gpus N` without a launcher starts the N ranks itself (torch.distributed.run, before anything
 touches the GPU); under a launcher it must equal WORLD_SIZE, and with RCCL every rank needs its own
@@ -142,6 +153,27 @@ def sha256_file(path):
     return h.hexdigest()
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all arrays of a run together stay well under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy: float64 for integer / float64 data (counters stay exact),
+    float32 otherwise.  An array over its share of DUMP_BUDGET_BYTES is cut to a fixed sample of its
+    rows (ascending row indices drawn by a generator seeded with the row count: the same rows for the
+    same shape in every run and build)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        wide = t.dtype in (torch.float64, torch.int64, torch.int32)
+        if t.dim() >= 1 and t.numel() * (8 if wide else 4) > share:
+            rows = max(share // ((8 if wide else 4) * (t.numel() // t.shape[0])), 1)
+            idx = np.sort(np.random.default_rng(t.shape[0]).choice(t.shape[0], rows, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        t = t.double() if wide else t.float()
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -156,8 +188,14 @@ def parse():
     ap.add_argument("--early-stop", choices=("off", "batch", "frame"), default="off",
                     help="min-sum / BP stopping rule: off (cfg3: every iteration), batch (the reference's "
                          "batch-global rule, traditional_decoders.py:104-107), frame (per-frame freeze)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline and report the PMC-based roofline figures "
+                         "(a plain run times the steps and prints the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float32 / "
+                         "float64; a fixed, seeded row sample of arrays over the size budget; rank 0's)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=10.0,
-                    help="target CPU work for the oracle baseline sample (0 disables)")
+                    help="with --full: target CPU work for the oracle baseline sample (0 disables)")
     ap.add_argument("--data", choices=("auto", "zero", "codewords"), default="auto",
                     help="transmitted frames: the all-zero codeword (every reference harness, e.g. "
                          "comparative_evaluation.py:133) or random codewords (utils/encoding.py), whose BER / "
@@ -168,7 +206,8 @@ def parse():
                     help="MessageGNN weights (a trainer checkpoint dict, loaded weights_only); default: "
                          "checkpoints/gnn_bg2_z<Z>_i<layers>_h64.pt when present, else random weights")
     ap.add_argument("--traffic-json", default=None,
-                    help="PMC traffic summary (profiles/*_pmc.json) to report as roofline.traffic")
+                    help="PMC traffic summary (profiles/*_pmc.json) to report as roofline.traffic "
+                         "(--full without it: the newest summary of the workload in profiles/)")
     return ap.parse_args()
 
 
@@ -418,6 +457,7 @@ def main():
     llr = awgn_llr(B, n, snr, seed=20251015, frame_offset=rank * B, bits=ref_bits, device=dev)
     counters = torch.zeros(4, dtype=torch.int64, device=dev)
     scratch = torch.zeros(4, dtype=torch.int64, device=dev)  # fused counters of a codeword run (iterations only)
+    last = {"counters": counters}  # what the last timed step hands its caller (--dump-outputs)
 
     weights = None
     if kind in ("minsum", "bp"):
@@ -426,6 +466,7 @@ def main():
                else BeliefPropagationDecoder(H, iters, early_stopping=False))
         g = dec.graph(dev)
         bits = torch.empty((B, n), dtype=torch.uint8, device=dev)
+        last["bits"] = bits  # every step decodes into this buffer
         algo = N.LDPC_ALGO_MINSUM if kind == "minsum" else N.LDPC_ALGO_BP
         stream = N.stream_ptr(dev)
         es = {"off": N.LDPC_ES_OFF, "batch": N.LDPC_ES_BATCH, "frame": N.LDPC_ES_FRAME}[a.early_stop]
@@ -461,6 +502,7 @@ def main():
         hdec, _ = create_custom_minsum_message_gnn_decoder(H, num_iterations=iters)
         g = hdec._graph(n, dev)
         probs = torch.empty((B, n), dtype=torch.float32, device=dev)
+        last["probs"] = probs  # every step decodes into this buffer
         wsb = N.check(N.lib().ldpc_custom_minsum_workspace_size(g.handle, B))
         ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
         stream = N.stream_ptr(dev)
@@ -497,7 +539,9 @@ def main():
                 for _ in range(iters):
                     v = rs(ellr, vl(ellr, ck(v, chk_d), var_d), prev)
                     prev = [v] + prev
-                ol(v, ellr)
+                soft, _ = ol(v, ellr)
+            if count:
+                last["soft"] = soft
 
         dtype = "f32"
         # per frame-iteration: read v + write c (check), read c + llr + write (variable),
@@ -546,6 +590,7 @@ def main():
             def step(count):
                 p, _ = hdec(llr, io, types, Avh, Ach)
                 if count:
+                    last["probs"] = p
                     count_errors((p > 0.5).to(torch.uint8), ref=ref_bits, counters=counters)
         elif kind == "gnn-sweep":
             from ldpc_neural_decoder.sweep import evaluate_message_gnn
@@ -564,12 +609,14 @@ def main():
                 loss.backward()
                 opt.step()
                 if count:
+                    last["probs"], last["loss"] = p, loss
                     from ldpc_neural_decoder.utils import count_errors
                     count_errors((p.detach() > 0.5).to(torch.uint8), ref=ref_bits, counters=counters)
         else:
             def step(count):
                 p = gdec.native_forward(llr, io, types, vg, cg)
                 if count:
+                    last["probs"] = p
                     from ldpc_neural_decoder.utils import count_errors
                     count_errors((p > 0.5).to(torch.uint8), ref=ref_bits, counters=counters)
 
@@ -653,6 +700,12 @@ def main():
     if kind.startswith("gnn") and kind != "gnn-train" and getattr(gdec, "last_iterations", None) is not None:
         avg_layers = float(gdec.last_iterations.double().mean())  # this rank's last step
     be, fe, fr, itsum = tot.tolist()
+    if a.dump_outputs and rank == 0:
+        if kind == "gnn-sweep":
+            last["ber"], last["fer"] = (torch.as_tensor(x, dtype=torch.float64) for x in sweep_out["ber_fer"])
+        if avg_layers is not None:
+            last["layers"] = gdec.last_iterations
+        dump_outputs(a.dump_outputs, last)
 
     if kind == "gnn-bf16" and avg_layers is not None:
         # early termination: the layers actually run (the frames' mean), not the maximum
@@ -663,6 +716,8 @@ def main():
         achieved = None if bound == "valu" else per_launch_alg / (kern_ms * 1e-3) / (1e9 if unit == "GB/s" else 1e12)
         traffic = None
         tj = a.traffic_json
+        if tj is None and not a.full:
+            tj = ""  # a plain run reports no PMC-based figure
         if tj is None:  # the newest PMC summary of this workload (profiles/<round>_pmc_<workload>.json)
             import glob
             import re
@@ -752,7 +807,7 @@ def main():
             notes = dict(notes or {}, ber_fer="not reported: random weights (no trained checkpoint for this "
                                               "configuration; tools/train_gnn_checkpoint.py makes one)")
         cpu = None
-        if world == 1 and a.cpu_baseline_seconds > 0:
+        if a.full and world == 1 and a.cpu_baseline_seconds > 0:
             cpu = cpu_baseline(a.workload, z, iters, a.cpu_baseline_seconds)
         out = {
             "metric": ("training codewords/s (BG2, %d layers, fwd+bwd+SGD)" % iters if kind == "gnn-train"

@@ -43,3 +43,27 @@ def test_gpus_2_without_gpus_exits_nonzero():
     if r.returncode == 0:
         pytest.fail("bench.py --gpus 2 succeeded without GPUs")
     assert r.returncode == 2 and "GPU(s) visible" in r.stderr, r.stderr[-1000:]
+
+
+def test_dump_outputs_formats_and_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 arrays (float64 for integer data, so counters stay exact), an array
+    over its share of the budget cut to the same ascending row sample in every run."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 16)
+    x = torch.arange(1000 * 64, dtype=torch.float32).reshape(1000, 64)
+    bits = (x % 2).to(torch.uint8)
+    counters = torch.tensor([3, 1, 1000, 2 ** 40 + 1])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "bits": bits, "counters": counters})
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("x", "bits", "counters")}
+    for n, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy")), n
+    assert got["counters"].dtype == np.float64 and got["counters"].tolist() == counters.tolist()
+    assert got["x"].dtype == np.float32 and got["bits"].dtype == np.float32
+    rows = (1 << 16) // 3 // (64 * 4)  # three arrays share the budget, 256 bytes per row
+    assert got["x"].shape == (rows, 64) and got["bits"].shape == (rows, 64)
+    idx = (got["x"][:, 0] / 64).astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(got["x"], x.numpy()[idx])
+    assert np.array_equal(got["bits"], bits.numpy()[idx].astype(np.float32))
+    assert sum(v.nbytes for v in got.values()) <= 1 << 16

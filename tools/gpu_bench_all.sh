@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/bench_all; mkdir -p $OUT
 cd $R
 run() {  # name, args...
   local n=$1; shift
-  timeout -k 10 400 python3 bench.py "$@" > $OUT/$n.json 2> $OUT/$n.err || { rc=$?; echo "bench $n rc=$rc"; tail -5 $OUT/$n.err; exit $rc; }
+  timeout -k 10 400 python3 bench.py --full "$@" > $OUT/$n.json 2> $OUT/$n.err || { rc=$?; echo "bench $n rc=$rc"; tail -5 $OUT/$n.err; exit $rc; }
   python3 -c "import json; d=json.load(open('$OUT/$n.json')); r=d['roofline']; c=d['cpu_baseline'] or {}; print('$n', round(d['value']), d['unit'], 'frac', None if r['frac'] is None else round(r['frac'],3), 'kern_ms', round(r['kernel_ms'],2), 'cpu', c.get('value'))"
 }
 run minsum-z32 --steps 20 --warmup 3

@@ -8,7 +8,7 @@ TAG=$T bash tools/gpu_evidence_y.sh profile || exit 1
 O=$R/gpurun_out/evidence_$T/bench; mkdir -p $O
 run() {  # name, args...
   local n=$1; shift
-  timeout -k 10 400 python3 bench.py "$@" > $O/$n.json 2> $O/$n.err || { rc=$?; echo "bench $n rc=$rc"; tail -5 $O/$n.err; exit $rc; }
+  timeout -k 10 400 python3 bench.py --full "$@" > $O/$n.json 2> $O/$n.err || { rc=$?; echo "bench $n rc=$rc"; tail -5 $O/$n.err; exit $rc; }
   python3 -c "import json; d=json.load(open('$O/$n.json')); r=d['roofline']; print('$n', round(d['value']), d['unit'], 'frac', None if r['frac'] is None else round(r['frac'],3), 'traffic', r.get('traffic'), 'kern_ms', round(r['kernel_ms'],2))"
 }
 run gnn-z32 --workload gnn-z32 --steps 3 --warmup 1 --cpu-baseline-seconds 10
