@@ -16,6 +16,8 @@
 //   var phase    each wave takes whole columns; a lane owns variable c*Z+t, reads its dv c2v
 //                (rotated slot index), writes v2c in place as the reference's ordered sums
 //   [ES]         decisions as 64-bit ballots per column in LDS, syndrome per block-row
+// (flood_kernel keeps every slot check-indexed and updates it in place, as above;
+// flood_fixed_kernel alternates the slot layout with the phase: "Slots" further down)
 //
 // Exactness: the reference sums/multiplies in float32 in a fixed order.  The var update is
 // v2c_i = (((llr + c_0) + c_1) ...) over i' != i in ascending check order; we compute it as the
@@ -108,6 +110,16 @@ struct Lane {
 };
 
 __device__ __forceinline__ float lds_rd(const char *lds, int off) { return *reinterpret_cast<const float *>(lds + off); }
+// read at an absolute LDS byte address (the low half of a generic pointer into LDS) plus a
+// compile-time offset: the offset lands in the instruction's immediate field and the address VGPR
+// is used as it is (through a generic pointer, every use of a kept address costs a v_add of the
+// LDS base, which the compiler rematerialises instead of keeping)
+typedef const __attribute__((address_space(3))) float lds_cf32;
+template <int OFF>
+__device__ __forceinline__ float lds_rd_abs(uint32_t addr) {
+    static_assert(OFF >= 0 && OFF < 65536, "ds offset is 16 bits");
+    return *(lds_cf32 *)(uintptr_t)(addr + OFF);
+}
 
 // ds_write_addtid_b32: LDS[M0 + OFF + 4 * lane] = v.  No address VGPR, and half the LDS cycles of a
 // ds_write_b32 (MI355X_MICROARCH.md, LDS table: 2 vs 4 per wave-instruction).  M0 must hold the
@@ -862,12 +874,34 @@ __global__ __launch_bounds__(512) void flood_kernel(FloodTables T, const float *
 // registers for the whole decode:
 //   ext[]   the channel LLRs of the wave's degree-1 edges (their v2c forever)
 //   cllr[]  the channel LLRs of the wave's columns
-//   rot[]   the rotated byte base f*Z + (k - s) mod Z of every shift s the wave's columns use
-// so the iteration touches no global memory and computes no addresses: a check-row message is
-// ds_read at lane4 + slot*256, a column message at rot[s] + slot*256 (immediate offsets).  Both
+//   rot[]   the rotated LDS address base + 4 (f*Z + (k - s) mod Z) of every rotation s the wave
+//           reads with
+// so the iteration touches no global memory and computes no addresses: every message is a
+// ds_read at rot[s] + slot*256 (immediate offsets) and a ds_write_addtid at slot*256.  Both
 // phases are software-pipelined: the next row's / column's LDS reads are issued before the
 // current one is computed (slots are disjoint between rows and between columns, so the reads
 // never depend on the writes in flight).  Bit-identical to flood_kernel.
+//
+// Slots.  Unlike flood_kernel's (always check-indexed) slots, a slot's layout here alternates with
+// the phase, so that every store is the own-lane ds_write_addtid_b32 (no address VGPR, half the
+// LDS cycles of a ds_write_b32 at a rotated address):
+//   after a check phase     check-indexed: position k holds the c2v of check row k
+//   after a variable phase  variable-indexed: position t holds the v2c of variable t (init too)
+// and both phases read rotated: the variable lane t reads position (t - s) mod Z, the check lane k
+// position (k + s) mod Z, which is the same rotation for the shift Z - s.  rot[] holds one entry
+// per distinct rotation of the wave's columns and rows (FxPlan::make).
+// Ordering.  Across waves nothing differs from in-place slots: in each phase a slot belongs to
+// one wave (its row's in the check phase, its column's in the variable phase) and the two barriers
+// separate the phases.  Inside the owning wave a lane now stores to a position that another lane
+// of the same wave reads, so every read of a slot must be issued before the first store to it.
+// A wave's DS instructions execute in issue order, and the compiler keeps the order because the
+// asm stores carry a "memory" clobber.  In the check phase every output of a row depends on every
+// input of the row, so data dependence gives the order as well.  In the variable phase output e
+// does not depend on input e: there the order rests on load_task reading the whole column before
+// task's first store, which is why a column's outputs are never split over two tasks
+// (static_assert in Task).  Reads issued ahead for the next row / task touch other slots.
+// The compiler does not count the asm stores in its lgkmcnt waits; LDS returns in order, so it can
+// only wait longer than needed, never shorter.
 namespace {
 
 
@@ -896,31 +930,40 @@ struct FxPlan {
     }
     struct Tab {
         int nsh = 0, next = 0, maxdc = 1, maxdv = 1;
-        int shv[64] = {};        // distinct shifts of the wave's columns
+        int shv[64] = {};        // distinct rotations the wave reads with (see make)
         int shidx[64] = {};      // shift -> index into shv (or -1)
         int ext_before[64] = {}; // ext edges in the wave's rows before row i
     };
+    // the rotation a check lane reads a variable-indexed slot with: row k of a block with shift s
+    // meets variable (k + s) mod Z, which is the variable side's rotation for shift Z - s
+    static constexpr int inv_shift(int s) { return (G::Z - s) % G::Z; }
+    // One rotation table per wave: the shifts of its columns (variable phase, lane t reads
+    // position (t - s) mod Z) and the inverse shifts of its rows' slot edges (check phase).
     static constexpr Tab make() {
         Tab t{};
         for (int i = 0; i < 64; ++i) t.shidx[i] = -1;
+        auto use = [&t](int s) {
+            if (t.shidx[s] < 0) {
+                t.shidx[s] = t.nsh;
+                t.shv[t.nsh++] = s;
+            }
+        };
+        for (int i = 0; i < NC; ++i) {
+            const int c = LDPC_VT(COLS)[C0 + i];
+            const int dv = G::COL_PTR[c + 1] - G::COL_PTR[c];
+            if (dv > t.maxdv) t.maxdv = dv;
+            for (int j = G::COL_PTR[c]; j < G::COL_PTR[c + 1]; ++j) use(G::COL_SHIFT[j]);
+        }
         for (int i = 0; i < NR; ++i) {
             const int R = G::CHK_ROWS[R0 + i];
             t.ext_before[i] = t.next;
             const int dc = G::ROW_PTR[R + 1] - G::ROW_PTR[R];
             if (dc > t.maxdc) t.maxdc = dc;
-            for (int e = G::ROW_PTR[R]; e < G::ROW_PTR[R + 1]; ++e)
-                if (G::ROW_SLOT[e] < 0) ++t.next;
-        }
-        for (int i = 0; i < NC; ++i) {
-            const int c = LDPC_VT(COLS)[C0 + i];
-            const int dv = G::COL_PTR[c + 1] - G::COL_PTR[c];
-            if (dv > t.maxdv) t.maxdv = dv;
-            for (int j = G::COL_PTR[c]; j < G::COL_PTR[c + 1]; ++j) {
-                const int s = G::COL_SHIFT[j];
-                if (t.shidx[s] < 0) {
-                    t.shidx[s] = t.nsh;
-                    t.shv[t.nsh++] = s;
-                }
+            for (int e = G::ROW_PTR[R]; e < G::ROW_PTR[R + 1]; ++e) {
+                if (G::ROW_SLOT[e] < 0)
+                    ++t.next;
+                else
+                    use(inv_shift(G::ROW_SHIFT[e]));
             }
         }
         return t;
@@ -953,7 +996,7 @@ struct FixedBody {
     static constexpr int MAXDC = P::T.maxdc, MAXDV = P::T.maxdv;
     float ext[NEXT];
     float cllr[NCOL];
-    int rot[NSH];
+    uint32_t rot[NSH];  // absolute LDS byte addresses (lds_rd_abs)
 
     __device__ __forceinline__ void init(Ctx &C, const Lane &L) {
         bool nan = false;
@@ -970,20 +1013,23 @@ struct FixedBody {
             });
         });
         sfor<P::T.nsh>([&](auto j) {
-            constexpr int J = decltype(j)::value;
-            rot[J] = L.fz4 + ((L.k4 + (4 * G::Z - 4 * P::T.shv[J])) & ZM4);
+            constexpr int J = decltype(j)::value, SH = P::T.shv[J];
+            const uint32_t base = (uint32_t)(uintptr_t)C.lds;
+            if constexpr (SH == 0)
+                rot[J] = opaque_vu(base + L.lane4);
+            else
+                rot[J] = opaque_vu(base + L.fz4 + ((L.k4 + (4 * G::Z - 4 * SH)) & ZM4));
         });
+        // the first v2c of an edge is its column's LLR: variable-indexed, so stored own-lane
+        addtid_begin(C.lds);
         sfor<P::NC>([&](auto i) {
             constexpr int I = decltype(i)::value, COL = LDPC_VT(COLS)[P::C0 + I];
             constexpr int P0 = G::COL_PTR[COL], DV = G::COL_PTR[COL + 1] - P0;
             cllr[I] = L.llr_at(COL * 4 * G::Z + L.k4);
             nan |= is_zero_sign(cllr[I]);
-            sfor<DV>([&](auto jj) {
-                constexpr int J = decltype(jj)::value, SL = G::COL_SLOT[P0 + J];
-                constexpr int SI = P::T.shidx[G::COL_SHIFT[P0 + J]];
-                lds_wr(C.lds + SL * 256, rot[SI], cllr[I]);
-            });
+            sfor<DV>([&](auto jj) { lds_wr_tid<G::COL_SLOT[P0 + decltype(jj)::value] * 256>(cllr[I]); });
         });
+        addtid_end();
         if (__any(nan) && L.lane == 0) *C.flag = 1;
     }
 
@@ -993,8 +1039,8 @@ struct FixedBody {
         constexpr int R = G::CHK_ROWS[P::R0 + I], P0 = G::ROW_PTR[R], DC = G::ROW_PTR[R + 1] - P0;
         sfor<DC>([&](auto e) {
             constexpr int E = decltype(e)::value, SL = G::ROW_SLOT[P0 + E];
-            if constexpr (SL >= 0)
-                v[E] = lds_rd(C.lds + SL * 256, L.lane4);
+            if constexpr (SL >= 0)  // variable-indexed slot: row k's edge is at position (k + s) mod Z
+                v[E] = lds_rd_abs<SL * 256>(rot[P::T.shidx[P::inv_shift(G::ROW_SHIFT[P0 + E])]]);
             else
                 v[E] = ext[P::ext_index(I, E)];
         });
@@ -1115,6 +1161,9 @@ struct FixedBody {
         static constexpr int PA = G::COL_PTR[CA], DA = G::COL_PTR[CA + 1] - PA;
         static constexpr int PB = CB >= 0 ? G::COL_PTR[CB] : 0, DB = CB >= 0 ? G::COL_PTR[CB + 1] - PB : 0;
         static_assert(DB <= DA && (DB == 0 || LO < DB), "pair tasks: A is the longer column, B has outputs");
+        // A task's stores turn its slots variable-indexed, so a second task over the same column
+        // would read its inputs in the wrong layout: a column's outputs are one task.
+        static_assert(LO == 0 && HI == DA, "a column split over two tasks needs its reads before any of its stores");
         static constexpr int IA = P::col_index(CA), IB = CB >= 0 ? P::col_index(CB) : 0;
         static constexpr int NPREFA = HI == DA ? DA : (HI > 0 ? HI - 1 : 0);
         static constexpr bool BLAST = DB > 0 && LO <= DB - 1 && DB - 1 < HI;  // B's APP here
@@ -1134,10 +1183,10 @@ struct FixedBody {
             constexpr int SA = G::COL_SLOT[K::PA + J], RA = P::T.shidx[G::COL_SHIFT[K::PA + J]];
             if constexpr (J < K::DB) {
                 constexpr int SB = G::COL_SLOT[K::PB + J], RB = P::T.shidx[G::COL_SHIFT[K::PB + J]];
-                in.cp[J].x = lds_rd(C.lds + SA * 256, rot[RA]);
-                in.cp[J].y = lds_rd(C.lds + SB * 256, rot[RB]);
+                in.cp[J].x = lds_rd_abs<SA * 256>(rot[RA]);
+                in.cp[J].y = lds_rd_abs<SB * 256>(rot[RB]);
             } else {
-                in.cs[J] = lds_rd(C.lds + SA * 256, rot[RA]);
+                in.cs[J] = lds_rd_abs<SA * 256>(rot[RA]);
             }
         });
     }
@@ -1183,16 +1232,18 @@ struct FixedBody {
         if constexpr (WRITE) {
             sfor<HI - LO>([&](auto q) {
                 constexpr int E = LO + decltype(q)::value;
-                constexpr int SA = G::COL_SLOT[K::PA + E], RA = P::T.shidx[G::COL_SHIFT[K::PA + E]];
+                // ds_write_addtid_b32: the v2c of variable t goes to position t, the slot turns
+                // variable-indexed (every read of it was issued by load_task, before this store)
+                constexpr int SA = G::COL_SLOT[K::PA + E];
                 if constexpr (E < DB) {
-                    constexpr int SB = G::COL_SLOT[K::PB + E], RB = P::T.shidx[G::COL_SHIFT[K::PB + E]];
-                    lds_wr(C.lds + SA * 256, rot[RA], acc2[E].x);
-                    lds_wr(C.lds + SB * 256, rot[RB], acc2[E].y);
+                    constexpr int SB = G::COL_SLOT[K::PB + E];
+                    lds_wr_tid<SA * 256>(acc2[E].x);
+                    lds_wr_tid<SB * 256>(acc2[E].y);
                     // smallest |v2c| written: a zero sets the flag (v_minimum3: no canonicalising
                     // v_max; a NaN here implies a non-finite APP, caught by `bad`)
                     if constexpr (ALGO == LDPC_ALGO_MINSUM) mz = vmin(vmin(mz, fabsf(acc2[E].x)), fabsf(acc2[E].y));
                 } else {
-                    lds_wr(C.lds + SA * 256, rot[RA], accA[E]);
+                    lds_wr_tid<SA * 256>(accA[E]);
                     if constexpr (ALGO == LDPC_ALGO_MINSUM) {
                         // two A-only outputs per v_minimum3
                         if constexpr ((E - (DB > LO ? DB : LO)) % 2 == 1)
@@ -1226,8 +1277,11 @@ struct FixedBody {
         if constexpr (P::NT > 0) {
             // software pipelining: the next task's reads are issued before the current task's adds
             // when the two hold at most kVarPipe messages together (slots are disjoint between
-            // tasks, so the reads never depend on the writes in flight)
+            // tasks, so the reads never depend on the writes in flight).  A task's own reads are
+            // all issued (load_task) before its first store: the stores land on positions that
+            // other lanes of this wave read (header comment, "Slots").
             TaskIn ta, tb;
+            if constexpr (WRITE) addtid_begin(C.lds);
             load_task<0>(C, ta);
             sfor<P::NT>([&](auto i) {
                 constexpr int I = decltype(i)::value;
@@ -1243,6 +1297,7 @@ struct FixedBody {
                     if constexpr (more && !ahead) load_task<(more ? I + 1 : I)>(C, ta);
                 }
             });
+            if constexpr (WRITE) addtid_end();
         }
         if constexpr (ALGO == LDPC_ALGO_MINSUM) {
             bad |= mz == 0.0f;
