@@ -66,7 +66,14 @@ struct Outs {
 // kTlWgs workgroups stores s_memtime at each phase boundary of the iteration loop -- after the
 // init barrier, then per iteration: check phase done, barrier 1 passed, variable phase done,
 // barrier 2 passed -- so the waves each barrier waits on can be read off.
-constexpr int kTlWgs = 2048, kTlMaxIter = 16, kTlPer = 2 + 4 * kTlMaxIter;
+// The last three words of a wave's row (flood_fixed_kernel only) bracket the loop: the stamp at
+// kernel entry (before make_lane), the stamp after the epilogue, and where the wave ran
+// (XCC_ID << 32 | HW_ID), so that prologue, epilogue and the gap between a workgroup's exit and
+// its successor's entry on the same CU can be read off.  The waves of one CU read the same
+// s_memtime counter; the counters of different CUs are far apart, even inside one XCC (measured:
+// ~2e8 units between the entry stamps of one generation), so stamps compare within a CU only.
+constexpr int kTlWgs = 2048, kTlMaxIter = 16, kTlTail = 3, kTlPer = 2 + 4 * kTlMaxIter + kTlTail;
+constexpr int kTlEntry = kTlPer - 3, kTlExit = kTlPer - 2, kTlWhere = kTlPer - 1;
 
 namespace {
 
@@ -108,6 +115,28 @@ struct Lane {
         return *reinterpret_cast<const float *>(llr_row + byte_off);
     }
 };
+
+#ifdef LDPC_TIMELINE
+__device__ __forceinline__ uint64_t tl_now() {
+    uint64_t t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+// entry / exit stamps and the place (XCC, SE, SH, CU, SIMD, wave slot) of this wave's decode
+__device__ __forceinline__ void tl_bracket(uint64_t *timeline, int wave, uint64_t t_in) {
+    const uint64_t t_out = tl_now();
+    uint32_t hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
+    if (timeline && blockIdx.x < (unsigned)kTlWgs && (threadIdx.x & 63) == 0) {
+        uint64_t *tl = timeline + ((int64_t)blockIdx.x * 4 + wave) * kTlPer;
+        tl[kTlEntry] = t_in;
+        tl[kTlExit] = t_out;
+        tl[kTlWhere] = ((uint64_t)xcc << 32) | hw;
+    }
+}
+#endif
 
 __device__ __forceinline__ float lds_rd(const char *lds, int off) { return *reinterpret_cast<const float *>(lds + off); }
 // read at an absolute LDS byte address (the low half of a generic pointer into LDS) plus a
@@ -740,7 +769,7 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (tl && k < kTlPer) tl[k] = t;
+        if (tl && k < kTlPer - kTlTail) tl[k] = t;
     };
 #else
     auto mark = [](int) {};
@@ -1347,12 +1376,24 @@ __global__ __launch_bounds__(256, ES == LDPC_ES_OFF ? 4 : 3) void flood_fixed_ke
                                                           int64_t B, int max_iter, float alpha, int out_dtype,
                                                           void *__restrict__ bits, Outs O, EsWs W) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const Lane L = make_lane(T, llr, B);
+#ifdef LDPC_TIMELINE
+    const uint64_t t_in = tl_now();
+#endif
+    // the code's dimensions are compile-time constants here: they need no SGPRs (the early-stop
+    // instances spilled VGPRs to scratch with the kernel-argument copies)
+    FloodTables Tc = T;
+    Tc.Z = G::Z, Tc.FG = 64 / G::Z, Tc.Mb = G::Mb, Tc.Nb = G::Nb, Tc.N = G::N, Tc.nslots = G::NSLOTS, Tc.W = G::W;
+    static_assert(G::Z < 64 && 64 % G::Z == 0, "rep1 below: a 1 at the bottom of every Z-bit segment");
+    Tc.rep1 = ~0ull / ((1ull << G::Z) - 1ull);
+    const Lane L = make_lane(Tc, llr, B);
     Ctx C;
-    init_ctx(C, T, lds, alpha, out_dtype, bits);
+    init_ctx(C, Tc, lds, alpha, out_dtype, bits);
     fx_by_wave<G>(__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), [&](auto wv) {
         FixedBody<G, ALGO, decltype(wv)::value> body;
         flood_drive<ES>(body, C, L, B, max_iter, O, W);
+#ifdef LDPC_TIMELINE
+        if constexpr (ES == LDPC_ES_OFF) tl_bracket(O.timeline, decltype(wv)::value, t_in);
+#endif
     });
 }
 
