@@ -35,7 +35,7 @@ enum {
     LDPC_ENOMEM = -4
 };
 
-enum { LDPC_ALGO_MINSUM = 0, LDPC_ALGO_BP = 1 };
+enum { LDPC_ALGO_MINSUM = 0, LDPC_ALGO_BP = 1, LDPC_ALGO_LAYERED_MINSUM = 2 };
 enum { LDPC_ES_OFF = 0, LDPC_ES_BATCH = 1, LDPC_ES_FRAME = 2 };
 enum { LDPC_OUT_U8 = 0, LDPC_OUT_F32 = 1 };
 
@@ -89,7 +89,30 @@ int ldpc_graph_edges(const ldpc_graph *g, int32_t *h_edge_chk, int32_t *h_edge_v
  *   counters are reduced through per-workgroup rows, not same-address atomics.
  * LDPC_ES_BATCH runs as passes on the stream (first all-valid iteration per workgroup, then the
  *   batch's candidate T, then -- only if some frame is invalid at T -- the exhaustive search);
- *   it never synchronises with the host. */
+ *   it never synchronises with the host.
+ *
+ * Layered min-sum (algo LDPC_ALGO_LAYERED_MINSUM; no reference counterpart, this text is its
+ * definition).  Row-serial scaled min-sum on the Tanner graph, all arithmetic float32 without fused
+ * multiply-add.  Per frame: app[v] = llr[v]; c2v[e] = +0 for every edge (check-major order).  One
+ * iteration visits the checks in ascending index; for check i with variables j_0 < ... < j_{d-1}:
+ *   1. t_k = app[j_k] - c2v[i,k]; for a variable of degree 1, t_k = llr[j_k] exactly (the flooding
+ *      decoders' rule that a degree-1 variable's v2c is the channel LLR forever);
+ *   2. c2v[i,k] = (prod_{q != k} sgn(t_q)) * (alpha * min_{q != k} |t_q|): the flooding min-sum
+ *      check rule, sgn(0) = sgn(NaN) = 0, the min starts at +inf and a NaN never wins it, the
+ *      product of signs is formed first and multiplied by alpha * min;
+ *   3. app[j_k] = t_k + c2v[i,k] (a degree-1 variable: llr + c2v, used for the decision only).
+ * After each full iteration bit[v] = (app[v] < 0).  The result depends on the graph alone, not on
+ * the lifting the library detects (the Z checks of a block row touch disjoint variables, so the
+ * kernel updates them at once).
+ * early_stop: LDPC_ES_OFF (every frame runs max_iter) or LDPC_ES_FRAME (a frame freezes at the
+ *   first iteration whose decisions satisfy H x = 0, with that iteration's bits and count, else
+ *   runs max_iter; d_batch_iters = the largest per-frame count).  LDPC_ES_BATCH exists to mirror
+ *   the reference's flooding classes: with this algo it is LDPC_EINVAL.
+ * LDS-resident only: a graph that the flooding algos decode on the streaming kernels (lifting not
+ *   a divisor of 64, LDS need above a CU's, or LDPC_FLOOD_STREAM set) is LDPC_EUNSUPPORTED.
+ * d_work: ldpc_flood_workspace_size of the same arguments suffices, when required as above.
+ * Non-finite LLRs: the call returns and every output is 0 or 1; the outputs of a frame holding a
+ *   NaN or an infinity are otherwise unspecified, the other frames of the batch are unaffected. */
 int64_t ldpc_flood_workspace_size(const ldpc_graph *g, int64_t B, int max_iter, int early_stop);
 int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_llr, int64_t B, int max_iter,
                       float alpha, int early_stop, int out_dtype, void *d_bits, int32_t *d_iters,

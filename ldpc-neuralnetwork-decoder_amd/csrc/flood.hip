@@ -23,7 +23,7 @@
 // tolerance", not bitwise).
 // Compile with -ffp-contract=off: no a*b+c may fuse on this path.
 // Translation units: flood_dev.hpp (device code shared by all), flood_fixed_ms.hip / flood_fixed_bp.hip
-// (compile-time schedules), flood_stream.hip (streaming decoders),
+// (compile-time schedules), flood_stream.hip (streaming decoders), flood_layered.hip (layered min-sum),
 // and this file (table-driven kernel, early-stop passes, host dispatch, the C ABI).
 #include <algorithm>
 #include <cstdio>
@@ -306,14 +306,30 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
                                  void *d_bits, int32_t *d_iters, int32_t *d_batch_iters,
                                  uint64_t *d_counters, void *d_work, int64_t work_bytes, void *stream) {
     if (!g) return fail(LDPC_EINVAL, "graph is NULL");
-    if (algo != LDPC_ALGO_MINSUM && algo != LDPC_ALGO_BP) return fail(LDPC_EINVAL, "unknown algo");
+    if (algo != LDPC_ALGO_MINSUM && algo != LDPC_ALGO_BP && algo != LDPC_ALGO_LAYERED_MINSUM)
+        return fail(LDPC_EINVAL, "unknown algo");
     if (early_stop < 0 || early_stop > 2) return fail(LDPC_EINVAL, "unknown early_stop mode");
     if (out_dtype != LDPC_OUT_U8 && out_dtype != LDPC_OUT_F32) return fail(LDPC_EINVAL, "unknown out_dtype");
     if (B < 0) return fail(LDPC_EINVAL, "negative batch");
     if (max_iter < 1 || max_iter > 1024) return fail(LDPC_EINVAL, "max_iter must be in [1, 1024]");
+    if (algo == LDPC_ALGO_LAYERED_MINSUM && early_stop == LDPC_ES_BATCH)
+        return fail(LDPC_EINVAL, "layered min-sum has no batch-global stop (LDPC_ES_BATCH mirrors the reference's "
+                                 "flooding classes): use LDPC_ES_OFF or LDPC_ES_FRAME");
     if (B == 0) return LDPC_OK;
     if (!d_llr || !d_bits) return fail(LDPC_EINVAL, "llr / bits is NULL");
     const bool streaming = use_stream(g, early_stop);
+    if (algo == LDPC_ALGO_LAYERED_MINSUM) {
+        // LDS-resident only: a streaming layered decoder would be one launch per layer
+        if (streaming)
+            return fail(LDPC_EUNSUPPORTED,
+                        "layered min-sum needs the LDS-resident schedule, and this graph decodes on the streaming "
+                        "kernels (lifting Z = " + std::to_string(g->Z) + (g->lds_ok ? "" : ", schedule encoding does not fit") +
+                        ", or LDPC_FLOOD_STREAM is set)");
+        if (!g->lt.prog || layered_lds_bytes(g, early_stop) > kLdsMax)
+            return fail(LDPC_EUNSUPPORTED, "layered min-sum: posteriors and messages of one wave's frames need " +
+                                               std::to_string(layered_lds_bytes(g, early_stop)) + " bytes of LDS, above " +
+                                               std::to_string(kLdsMax));
+    }
     if (streaming && (g->max_dv > kStreamMaxDeg || g->max_dc > kStreamMaxDeg))
         return fail(LDPC_EUNSUPPORTED, "streaming decoder: node degree above " + std::to_string(kStreamMaxDeg));
     // scratch is needed by the streaming decoder, the batch-global stop and any counter output
@@ -327,6 +343,9 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
         hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(1), 0, s, d_batch_iters, max_iter);
         LDPC_CHECK_LAUNCH("fill");
     }
+    if (algo == LDPC_ALGO_LAYERED_MINSUM)
+        return run_layered(g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits, d_iters, d_counters,
+                           d_batch_iters, d_work, s);
     if (streaming)
         return algo == LDPC_ALGO_MINSUM
                    ? run_stream_decode(LDPC_ALGO_MINSUM, g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits,

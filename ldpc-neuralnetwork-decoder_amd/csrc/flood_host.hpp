@@ -23,6 +23,12 @@ int launch_fixed_bp(int fixed_id, int es, dim3 grid, dim3 block, size_t lds, hip
                     const float *llr, int64_t B, int max_iter, float alpha, int out_dtype, void *bits, const Outs &O,
                     const EsWs &W);
 
+// flood_layered.hip: layered min-sum (LDS-resident only; es is LDPC_ES_OFF or LDPC_ES_FRAME).  work holds the
+// counter rows, one per FG frames: the head of the flooding workspace of the same arguments.
+size_t layered_lds_bytes(const ldpc_graph *g, int es);
+int run_layered(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int es, int out_dtype,
+                void *bits, int32_t *iters_out, uint64_t *counters, int32_t *batch_iters, void *work, hipStream_t s);
+
 // flood_stream.hip: the streaming decoders (messages in HBM, any graph)
 int64_t stream_ws_bytes(const ldpc_graph *g, int64_t B, int max_iter);
 int run_stream_decode(int algo, const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int es,

@@ -219,6 +219,26 @@ int build(ldpc_graph *g) {
         return off;
     };
     const size_t o_c = put(chk), o_v = put(var), o_p = put(par), o_b = put(bw_task), o_pp = put(prog_ptr);
+    // layered schedule (LayeredTables): block rows ascending, posteriors of columns with degree != 1
+    std::vector<int32_t> lay, lay_cols, post_of(Nb, -1);
+    for (int c = 0; c < Nb; ++c)
+        if (dv[c] != 1) { post_of[c] = (int32_t)lay_cols.size(); lay_cols.push_back(c); }
+    const bool lay_ok = (int64_t)lay_cols.size() * 256 < (1 << kShiftBit);
+    for (int r = 0; r < Mb && lay_ok; ++r) {
+        lay.push_back((int32_t)row_blocks[r].size());
+        int32_t first = 0;
+        for (int i : row_blocks[r])
+            if (slot_of[i] >= 0) { first = slot_of[i] * 256; break; }
+        lay.push_back(first);
+        for (int i : row_blocks[r]) {
+            const Block &bk = blocks[i];
+            if (slot_of[i] >= 0)
+                lay.push_back((post_of[bk.c] * 256) | ((4 * bk.s) << kShiftBit));
+            else
+                lay.push_back(kExtFlag | bk.c | ((4 * bk.s) << kShiftBit));
+        }
+    }
+    const size_t o_l = put(lay), o_lc = put(lay_cols);
     LDPC_HIP(hipGetDevice(&g->device));
     LDPC_HIP(hipMalloc(&g->d_tab, blob.size() * sizeof(int32_t)));
     LDPC_HIP(hipMemcpy(g->d_tab, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -237,6 +257,11 @@ int build(ldpc_graph *g) {
     t.W = W;
     t.rep1 = 0;
     for (int b = 0; b < 64; b += g->Z) t.rep1 |= 1ull << b;
+    if (lay_ok) {
+        g->lt.prog = g->d_tab + o_l;
+        g->lt.cols = g->d_tab + o_lc;
+        g->lt.ncols = (int)lay_cols.size();
+    }
 
     // compile-time schedule available for this exact graph (and the default 4 waves)?
     auto matches = [&](auto tag) {

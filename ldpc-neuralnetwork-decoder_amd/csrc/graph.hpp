@@ -44,6 +44,19 @@ constexpr int32_t kLowMask = (1 << kShiftBit) - 1;
 
 struct Block { int r, c, s; };
 
+// Device view of the layered schedule (flood_layered.hip): the block rows in ascending order, each
+// one a layer.  Columns with degree != 1 own one posterior slot of 64 floats, column-indexed
+// (position f*Z + t holds variable c*Z + t of frame f); cols lists them in slot order.
+//   prog, per block-row: header dc, byte offset of the row's first c2v slot, then dc edge words
+//       posterior edge: posterior_slot_byte_offset | (4*shift) << 18
+//       degree-1:       0x80000000 | col | (4*shift) << 18   (its input is the channel LLR)
+//   the c2v slots of a row's posterior edges are consecutive (FloodTables' slot numbering is
+//   row-major)
+struct LayeredTables {
+    const int32_t *prog, *cols;
+    int ncols;
+};
+
 }  // namespace ldpc
 
 struct ldpc_graph {
@@ -60,6 +73,7 @@ struct ldpc_graph {
     int fixed_id = 0;      // 0: table-driven kernel; 1/2: compile-time schedule BG2_Z4 / BG2_Z32
     int fixed_match = 0;   // what the graph matched (kept when the variant is forced off)
     bool lds_ok = true;    // the LDS-resident schedule exists (its encoding fits); else stream only
+    ldpc::LayeredTables lt{};  // layered schedule (prog == nullptr: its encoding does not fit)
     // streaming decoder (flood.hip, any graph): check-major CSR + per-variable edge lists
     int32_t *d_csr = nullptr;  // chk_ptr[M+1] edge_var[E] var_ptr[N+1] var_edge[E]
     const int32_t *chk_ptr = nullptr, *ev = nullptr, *var_ptr = nullptr, *var_edge = nullptr;

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDPC_AMD_LIB", os.path.join(_HERE, "_lib", "libldpc_amd.so"))
 
-LDPC_ALGO_MINSUM, LDPC_ALGO_BP = 0, 1
+LDPC_ALGO_MINSUM, LDPC_ALGO_BP, LDPC_ALGO_LAYERED_MINSUM = 0, 1, 2
 LDPC_ES_OFF, LDPC_ES_BATCH, LDPC_ES_FRAME = 0, 1, 2
 LDPC_OUT_U8, LDPC_OUT_F32 = 0, 1
 LDPC_GNN_EARLY_STOP = 1

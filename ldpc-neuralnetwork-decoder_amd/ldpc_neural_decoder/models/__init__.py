@@ -2,7 +2,7 @@
 from ldpc_neural_decoder.models.layers import CheckLayer, VariableLayer, ResidualLayer, OutputLayer
 from ldpc_neural_decoder.models.decoder import LDPCNeuralDecoder
 from ldpc_neural_decoder.models.traditional_decoders import (
-    BeliefPropagationDecoder, MinSumScaledDecoder)
+    BeliefPropagationDecoder, LayeredMinSumDecoder, MinSumScaledDecoder)
 from ldpc_neural_decoder.models.message_gnn_decoder import (
     MessageGNNLayer, MessageGNNDecoder, TannerToMessageGraph, create_message_gnn_decoder)
 from ldpc_neural_decoder.models.custom_decoders import (
@@ -12,7 +12,7 @@ from ldpc_neural_decoder.models.custom_decoders import (
 
 __all__ = [
     "CheckLayer", "VariableLayer", "ResidualLayer", "OutputLayer", "LDPCNeuralDecoder",
-    "BeliefPropagationDecoder", "MinSumScaledDecoder",
+    "BeliefPropagationDecoder", "MinSumScaledDecoder", "LayeredMinSumDecoder",
     "MessageGNNLayer", "MessageGNNDecoder", "TannerToMessageGraph", "create_message_gnn_decoder",
     "CustomCheckMessageGNNLayer", "CustomMinSumMessageGNNDecoder", "CustomVariableMessageGNNLayer",
     "create_custom_minsum_message_gnn_decoder", "CustomVariableMessageGNNDecoder",

@@ -126,3 +126,27 @@ class MinSumScaledDecoder(_FloodDecoder):
 
     def _alpha(self):
         return self.scaling_factor
+
+
+class LayeredMinSumDecoder(_FloodDecoder):
+    """Layered (row-serial) scaled min-sum: the checks are visited in ascending index and each sees
+    the posteriors its predecessors just updated (the algorithm is written out in
+    include/ldpc_amd.h; csrc/flood_layered.hip).  No reference counterpart.
+
+    Same ``decode`` / ``decode_async`` contract, ``out_dtype``, ``counters`` and
+    ``return_frame_iters`` as the two flooding classes.  Where it differs from them:
+    ``early_stopping=True`` and ``early_stopping="frame"`` BOTH mean the per-frame freeze (a frame
+    stops at the first iteration whose decisions satisfy H x = 0); there is no batch-global rule,
+    and ``iterations`` is then the largest per-frame count.  A graph without an LDS-resident
+    schedule (e.g. a lifting size that does not divide 64) raises ``NativeError``."""
+    _algo = N.LDPC_ALGO_LAYERED_MINSUM
+
+    def __init__(self, H, max_iterations=50, scaling_factor=0.75, early_stopping=True):
+        self.scaling_factor = scaling_factor
+        super().__init__(H, max_iterations, early_stopping)
+
+    def _alpha(self):
+        return self.scaling_factor
+
+    def _es_mode(self):
+        return N.LDPC_ES_FRAME if self.early_stopping else N.LDPC_ES_OFF
