@@ -924,10 +924,12 @@ __global__ __launch_bounds__(512) void flood_kernel(FloodTables T, const float *
 // separate the phases.  Inside the owning wave a lane now stores to a position that another lane
 // of the same wave reads, so every read of a slot must be issued before the first store to it.
 // A wave's DS instructions execute in issue order, and the compiler keeps the order because the
-// asm stores carry a "memory" clobber.  In the check phase every output of a row depends on every
-// input of the row, so data dependence gives the order as well.  In the variable phase output e
-// does not depend on input e: there the order rests on load_task reading the whole column before
-// task's first store, which is why a column's outputs are never split over two tasks
+// asm stores carry a "memory" clobber.  In the check phase a two-minimum row's outputs depend on
+// every input of the row, so data dependence gives the order as well; a directly computed row's
+// output e (LDPC_DIRECT_DC) does not depend on input e, and there the order rests on load_row
+// reading the whole row before row's first store.  In the variable phase output e
+// does not depend on input e either: there the order rests on load_task reading the whole column
+// before task's first store, which is why a column's outputs are never split over two tasks
 // (static_assert in Task).  Reads issued ahead for the next row / task touch other slots.
 // The compiler does not count the asm stores in its lgkmcnt waits; LDS returns in order, so it can
 // only wait longer than needed, never shorter.
@@ -1015,6 +1017,54 @@ struct FxPlan {
 // at most this many messages together (register budget: 4 workgroups per CU = 128 VGPRs)
 constexpr int kVarPipe = LDPC_VAR_PIPE;
 
+// Min-sum check rows of degree 2 .. LDPC_DIRECT_DC compute every output directly from the other
+// inputs on the fast path (direct_row); longer rows keep the two-minimum / select form.
+// 0 restores the select form for every row (A/B builds).
+#ifndef LDPC_DIRECT_DC
+#define LDPC_DIRECT_DC 6
+#endif
+constexpr int kDirectDc = LDPC_DIRECT_DC;
+static_assert(kDirectDc >= 0 && kDirectDc <= 6, "direct_row is written out for degrees 2 .. 6");
+
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
+
+// Output E of a min-sum row of degree DC with no zero and no NaN message, without the two minima:
+//   c2v_E = (xor of the other inputs' sign bits) ^ (alpha * min of the other inputs' magnitudes)
+// The excluded minimum |x_E| == m1 ? m2 : m1 of the select form is this minimum as a float (a tie
+// at m1 puts m1 in m2), the product is the same single multiply, and the sign is the same xor: bit
+// for bit the select form, with no compare into an SGPR pair and no v_cndmask.
+//   DC <= 4  v_min / v_minimum3 and v_xor / v_bitop3 over the 1 .. 3 other inputs, alpha * min,
+//            then product ^ (xor & sign mask) as one v_bitop3 (0x78)
+//   DC >= 5  pair minima pr[] = min(|x_2j|, |x_2j+1|) shared by the row, one v_minimum3 over the
+//            pair partner and the other pairs (or the odd input) per output; the row's parity goes
+//            into alpha's sign once (als: (-alpha) * m = -(alpha * m) exactly), so an output is
+//            minimum3, multiply and product ^ (x_E & sign mask)
+template <int DC, int E, int CAP>
+__device__ __forceinline__ float direct_row(const float (&v)[CAP], const float (&pr)[3], float als, float alv, uint32_t sgn) {
+    static_assert(DC >= 2 && DC <= 6 && E < DC && DC <= CAP, "direct form: degrees 2 .. 6");
+    constexpr int A = E == 0 ? 1 : 0, B = E <= 1 ? 2 : 1, Cc = E <= 2 ? 3 : 2;  // the first other inputs
+    auto bits = [&](int e) { return __float_as_uint(v[e]); };
+    if constexpr (DC == 2) {
+        return __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(alv * fabsf(v[A])), bits(A), sgn, 0x78));
+    } else if constexpr (DC == 3) {
+        const float m = vmin(fabsf(v[A]), fabsf(v[B]));
+        return __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(alv * m), bits(A) ^ bits(B), sgn, 0x78));
+    } else if constexpr (DC == 4) {
+        const float m = vmin(vmin(fabsf(v[A]), fabsf(v[B])), fabsf(v[Cc]));
+        return __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(alv * m), xor3(bits(A), bits(B), bits(Cc)), sgn, 0x78));
+    } else {
+        constexpr int PE = E / 2;  // E's pair; DC == 5: input 4 has none
+        float m;
+        if constexpr (DC == 5 && E == 4)
+            m = vmin(pr[0], pr[1]);
+        else if constexpr (DC == 5)
+            m = vmin(vmin(fabsf(v[E ^ 1]), pr[1 - PE]), fabsf(v[4]));
+        else
+            m = vmin(vmin(fabsf(v[E ^ 1]), pr[(PE + 1) % 3]), pr[(PE + 2) % 3]);
+        return __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(als * m), bits(E), sgn, 0x78));
+    }
+}
+
 template <class G, int ALGO, int WV>
 struct FixedBody {
     using P = FxPlan<G, WV>;
@@ -1089,7 +1139,28 @@ struct FixedBody {
                     ext_decision(C, L, G::ROW_COL[P0 + E], 4 * G::ROW_SHIFT[P0 + E], v[E] + o, errs);
             }
         };
-        if constexpr (ALGO == LDPC_ALGO_MINSUM) {
+        if constexpr (ALGO == LDPC_ALGO_MINSUM && !SLOW && DC >= 2 && DC <= kDirectDc) {
+            // short row on the fast path (no zero, no NaN: the sticky flag, see below): every
+            // output straight from the other inputs, see direct_row
+            float pr[3] = {};
+            float als = alv;
+            if constexpr (DC >= 5) {
+                sfor<DC / 2>([&](auto j) {
+                    constexpr int J = decltype(j)::value;
+                    pr[J] = vmin(fabsf(v[2 * J]), fabsf(v[2 * J + 1]));
+                });
+                uint32_t par = xor3(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]));
+                if constexpr (DC == 5)
+                    par = xor3(par, __float_as_uint(v[3]), __float_as_uint(v[4]));
+                else
+                    par = xor3(par, __float_as_uint(v[3]), __float_as_uint(v[4])) ^ __float_as_uint(v[5]);
+                als = __uint_as_float(__builtin_amdgcn_bitop3_b32(__float_as_uint(alv), par, sgn, 0x78));
+            }
+            sfor<DC>([&](auto e) {
+                constexpr int E = decltype(e)::value;
+                if constexpr (needed(E)) emit(e, direct_row<DC, E>(v, pr, als, alv, sgn));
+            });
+        } else if constexpr (ALGO == LDPC_ALGO_MINSUM) {
             // the two smallest magnitudes (v_med3 / v_min with |x| source modifiers)
             // m2 starts as an opaque +inf: a constant one lets the compiler rewrite the first
             // v_med3 as a canonicalising fmaxf

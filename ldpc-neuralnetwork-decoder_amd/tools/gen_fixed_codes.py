@@ -20,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CODES = [("BG2_Z4", os.path.join(ROOT, "codes", "NR_2_0_4.txt"), 4),
          ("BG2_Z32", os.path.join(ROOT, "codes", "NR_2_0_32.txt"), 32)]
 W = 4
+DIRECT_DC = 6  # the default of LDPC_DIRECT_DC in csrc/flood_dev.hpp
 
 
 def load(path):
@@ -106,8 +107,9 @@ def gen(name, base, z):
     # per-iteration SIMD pipe cycles of one wave's share (tools/ubench costs at 4 waves / SIMD):
     # check row: the two minima (half-rate min / med3), sign parity, per slot edge compare +
     # select + sign, row constants; column: the exclusive ordered sums (full-rate adds) + its LDS
-    # reads / writes issued
-    rcost = [4.1 * n_min_ops(dc[r]) + 2.2 * (dc[r] // 2) + 10.4 * nslot[r] + 12 + 2.0 * dc[r] for r in rows]
+    # reads / writes issued.  Rows of degree <= DIRECT_DC take the direct form (direct_row_cost).
+    rcost = [direct_row_cost(dc[r], nslot[r]) if 2 <= dc[r] <= DIRECT_DC else
+             4.1 * n_min_ops(dc[r]) + 2.2 * (dc[r] // 2) + 10.4 * nslot[r] + 12 + 2.0 * dc[r] for r in rows]
     vcols = [c for c in range(nb) if dv[c] != 1]
     chk = balance(rows, rcost, W)
     vt_pair = var_schedule(vcols, dv, W, pairs=True)
@@ -172,6 +174,20 @@ def n_min_ops(d):
     if d == 2:
         return 2
     return 2 + 5 * ((d - 3) // 3) + 2 * ((d - 3) % 3)
+
+
+def direct_row_cost(d, nout):
+    """SIMD pipe cycles of a min-sum row of degree d <= DIRECT_DC with nout outputs in the direct
+    form (flood_dev.hpp direct_row), same unit costs as above: 4.1 per half-rate min / minimum3,
+    2.2 per full-rate multiply / xor / bitop3, 2.0 per edge.
+    d <= 4: per output a minimum over the other inputs, their sign xor, alpha * min, sign merge.
+    d >= 5: per row d // 2 pair minima, the parity (one 3-input xor per two inputs) and alpha's
+    sign; per output one minimum3, the product and the sign merge."""
+    if d <= 4:
+        row, out = 0.0, (4.1 if d >= 3 else 0.0) + (2.2 if d >= 3 else 0.0) + 2 * 2.2
+    else:
+        row, out = 4.1 * (d // 2) + 2.2 * (d // 2) + 2.2, 4.1 + 2 * 2.2
+    return row + out * nout + 2.0 * d
 
 
 def var_task_ops(DA, DB, lo, hi):

@@ -12,7 +12,7 @@ LDPC_FLOOD_KERNELS_ONLY and instantiates flood_fixed_kernel<BG2_Z32, MINSUM, ES_
 import re
 import sys
 
-HALF = ("v_min_", "v_max_", "v_med3_", "v_cmp_", "v_cndmask_", "v_bfi_", "v_readfirstlane", "v_readlane", "v_writelane",
+HALF = ("v_min_", "v_max_", "v_minimum", "v_maximum", "v_med3_","v_cmp_", "v_cndmask_", "v_bfi_", "v_readfirstlane", "v_readlane", "v_writelane",
         "v_exp_", "v_log_", "v_rcp_", "v_rsq_", "v_sqrt_")  # transcendentals: 4 at 4 waves/SIMD (8 alone)
 
 
