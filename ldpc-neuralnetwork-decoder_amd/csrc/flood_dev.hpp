@@ -905,6 +905,9 @@ __global__ __launch_bounds__(512) void flood_kernel(FloodTables T, const float *
 //   cllr[]  the channel LLRs of the wave's columns
 //   rot[]   the rotated LDS address base + 4 (f*Z + (k - s) mod Z) of every rotation s the wave
 //           reads with
+//   msg[]   the messages of the wave's register edges (LDPC_REG_EDGES further down): edges whose
+//           check lane and variable lane are the same lane of this wave, so the message never
+//           leaves its VGPR -- no slot traffic, no rotation
 // so the iteration touches no global memory and computes no addresses: every message is a
 // ds_read at rot[s] + slot*256 (immediate offsets) and a ds_write_addtid at slot*256.  Both
 // phases are software-pipelined: the next row's / column's LDS reads are issued before the
@@ -919,7 +922,9 @@ __global__ __launch_bounds__(512) void flood_kernel(FloodTables T, const float *
 // and both phases read rotated: the variable lane t reads position (t - s) mod Z, the check lane k
 // position (k + s) mod Z, which is the same rotation for the shift Z - s.  rot[] holds one entry
 // per distinct rotation of the wave's columns and rows (FxPlan::make).
-// Ordering.  Across waves nothing differs from in-place slots: in each phase a slot belongs to
+// Ordering.  All of this is about LDS slots: a register edge's message is a VGPR that one lane
+// writes and the same lane reads, ordered by the program like any other value (its slot number
+// stays allocated and unused).  Across waves nothing differs from in-place slots: in each phase a slot belongs to
 // one wave (its row's in the check phase, its column's in the variable phase) and the two barriers
 // separate the phases.  Inside the owning wave a lane now stores to a position that another lane
 // of the same wave reads, so every read of a slot must be issued before the first store to it.
@@ -947,10 +952,39 @@ namespace {
 #define LDPC_VT(x) G::VS_##x
 #endif
 
+// Register edges (gen/fixed_codes.hpp RE_*, tools/gen_fixed_codes.py reg_edge_schedule): the checks
+// of every block row are relabelled by an offset rho_r, so that the kernel sees the shifts
+// (s + rho_r) mod Z -- the same code, the same operation order -- and an edge whose normalised shift
+// is 0, with its row and its column on one wave, keeps its message in a VGPR (msg[]) of that lane
+// instead of an LDS slot.  0 reads the schedule without them (A/B builds); the unpaired variable
+// schedule has none either (the RE_* arrays are chosen for the waves of VT's columns).
+#ifndef LDPC_REG_EDGES
+#define LDPC_REG_EDGES LDPC_VAR_PAIRS
+#endif
+#if LDPC_REG_EDGES && !LDPC_VAR_PAIRS
+#error "LDPC_REG_EDGES=1 needs the paired variable schedule (LDPC_VAR_PAIRS=1)"
+#endif
+
 // per-wave compile-time plan
 template <class G, int WV>
 struct FxPlan {
-    static constexpr int R0 = G::CHK_PTR[WV], NR = G::CHK_PTR[WV + 1] - R0;
+#if LDPC_REG_EDGES
+    static constexpr int R0 = G::RE_CHK_PTR[WV], NR = G::RE_CHK_PTR[WV + 1] - R0, NREG = G::RE_NREG[WV];
+    static constexpr int chk_row(int i) { return G::RE_CHK_ROWS[R0 + i]; }
+    // by edge index in row order (ROW_*) / in column order (COL_*): the normalised shift, and the
+    // edge's index into msg[] (-1: the message lives in its LDS slot)
+    static constexpr int row_shift(int e) { return G::RE_ROW_SHIFT[e]; }
+    static constexpr int col_shift(int j) { return G::RE_COL_SHIFT[j]; }
+    static constexpr int row_reg(int e) { return G::RE_ROW_REG[e]; }
+    static constexpr int col_reg(int j) { return G::RE_COL_REG[j]; }
+#else
+    static constexpr int R0 = G::CHK_PTR[WV], NR = G::CHK_PTR[WV + 1] - R0, NREG = 0;
+    static constexpr int chk_row(int i) { return G::CHK_ROWS[R0 + i]; }
+    static constexpr int row_shift(int e) { return G::ROW_SHIFT[e]; }
+    static constexpr int col_shift(int j) { return G::COL_SHIFT[j]; }
+    static constexpr int row_reg(int) { return -1; }
+    static constexpr int col_reg(int) { return -1; }
+#endif
     // the wave's columns (LLRs in registers, init, shifts) and its variable tasks
     static constexpr int C0 = LDPC_VT(COL_PTR)[WV], NC = LDPC_VT(COL_PTR)[WV + 1] - C0;
     static constexpr int T0 = LDPC_VT(PTR)[WV], NT = LDPC_VT(PTR)[WV + 1] - T0;
@@ -983,18 +1017,19 @@ struct FxPlan {
             const int c = LDPC_VT(COLS)[C0 + i];
             const int dv = G::COL_PTR[c + 1] - G::COL_PTR[c];
             if (dv > t.maxdv) t.maxdv = dv;
-            for (int j = G::COL_PTR[c]; j < G::COL_PTR[c + 1]; ++j) use(G::COL_SHIFT[j]);
+            for (int j = G::COL_PTR[c]; j < G::COL_PTR[c + 1]; ++j)
+                if (col_reg(j) < 0) use(col_shift(j));
         }
         for (int i = 0; i < NR; ++i) {
-            const int R = G::CHK_ROWS[R0 + i];
+            const int R = chk_row(i);
             t.ext_before[i] = t.next;
             const int dc = G::ROW_PTR[R + 1] - G::ROW_PTR[R];
             if (dc > t.maxdc) t.maxdc = dc;
             for (int e = G::ROW_PTR[R]; e < G::ROW_PTR[R + 1]; ++e) {
                 if (G::ROW_SLOT[e] < 0)
                     ++t.next;
-                else
-                    use(inv_shift(G::ROW_SHIFT[e]));
+                else if (row_reg(e) < 0)
+                    use(inv_shift(row_shift(e)));
             }
         }
         return t;
@@ -1002,7 +1037,7 @@ struct FxPlan {
     static constexpr Tab T = make();
     // index into ext[] of edge e of the wave's row i (an edge without a slot)
     static constexpr int ext_index(int i, int e) {
-        const int R = G::CHK_ROWS[R0 + i];
+        const int R = chk_row(i);
         int x = T.ext_before[i];
         for (int q = 0; q < e; ++q)
             if (G::ROW_SLOT[G::ROW_PTR[R] + q] < 0) ++x;
@@ -1073,19 +1108,21 @@ struct FixedBody {
     static constexpr int NCOL = P::NC > 0 ? P::NC : 1;
     static constexpr int NSH = P::T.nsh > 0 ? P::T.nsh : 1;
     static constexpr int MAXDC = P::T.maxdc, MAXDV = P::T.maxdv;
+    static constexpr int NRG = P::NREG > 0 ? P::NREG : 1;
     float ext[NEXT];
     float cllr[NCOL];
     uint32_t rot[NSH];  // absolute LDS byte addresses (lds_rd_abs)
+    float msg[NRG];     // the messages of the wave's register edges: v2c after init / var, c2v after check
 
     __device__ __forceinline__ void init(Ctx &C, const Lane &L) {
         bool nan = false;
         sfor<P::NR>([&](auto i) {
-            constexpr int I = decltype(i)::value, R = G::CHK_ROWS[P::R0 + I];
+            constexpr int I = decltype(i)::value, R = P::chk_row(I);
             constexpr int P0 = G::ROW_PTR[R], DC = G::ROW_PTR[R + 1] - P0;
             sfor<DC>([&](auto e) {
                 constexpr int E = decltype(e)::value;
                 if constexpr (G::ROW_SLOT[P0 + E] < 0) {
-                    constexpr int X = P::ext_index(I, E), COL = G::ROW_COL[P0 + E], S4 = 4 * G::ROW_SHIFT[P0 + E];
+                    constexpr int X = P::ext_index(I, E), COL = G::ROW_COL[P0 + E], S4 = 4 * P::row_shift(P0 + E);
                     ext[X] = L.llr_at(COL * 4 * G::Z + ((L.k4 + S4) & ZM4));
                     nan |= is_zero_sign(ext[X]);  // zero or NaN: the sticky flag (see check())
                 }
@@ -1099,14 +1136,21 @@ struct FixedBody {
             else
                 rot[J] = opaque_vu(base + L.fz4 + ((L.k4 + (4 * G::Z - 4 * SH)) & ZM4));
         });
-        // the first v2c of an edge is its column's LLR: variable-indexed, so stored own-lane
+        // the first v2c of an edge is its column's LLR: variable-indexed, so stored own-lane (a
+        // register edge's variable lane is its check lane: the LLR goes into msg[], no store)
         addtid_begin(C.lds);
         sfor<P::NC>([&](auto i) {
             constexpr int I = decltype(i)::value, COL = LDPC_VT(COLS)[P::C0 + I];
             constexpr int P0 = G::COL_PTR[COL], DV = G::COL_PTR[COL + 1] - P0;
             cllr[I] = L.llr_at(COL * 4 * G::Z + L.k4);
             nan |= is_zero_sign(cllr[I]);
-            sfor<DV>([&](auto jj) { lds_wr_tid<G::COL_SLOT[P0 + decltype(jj)::value] * 256>(cllr[I]); });
+            sfor<DV>([&](auto jj) {
+                constexpr int J = P0 + decltype(jj)::value;
+                if constexpr (P::col_reg(J) >= 0)
+                    msg[P::col_reg(J)] = cllr[I];
+                else
+                    lds_wr_tid<G::COL_SLOT[J] * 256>(cllr[I]);
+            });
         });
         addtid_end();
         if (__any(nan) && L.lane == 0) *C.flag = 1;
@@ -1115,28 +1159,32 @@ struct FixedBody {
     // ---- check phase
     template <int I>
     __device__ __forceinline__ void load_row(const Ctx &C, const Lane &L, float (&v)[MAXDC]) const {
-        constexpr int R = G::CHK_ROWS[P::R0 + I], P0 = G::ROW_PTR[R], DC = G::ROW_PTR[R + 1] - P0;
+        constexpr int R = P::chk_row(I), P0 = G::ROW_PTR[R], DC = G::ROW_PTR[R + 1] - P0;
         sfor<DC>([&](auto e) {
             constexpr int E = decltype(e)::value, SL = G::ROW_SLOT[P0 + E];
-            if constexpr (SL >= 0)  // variable-indexed slot: row k's edge is at position (k + s) mod Z
-                v[E] = lds_rd_abs<SL * 256>(rot[P::T.shidx[P::inv_shift(G::ROW_SHIFT[P0 + E])]]);
+            if constexpr (P::row_reg(P0 + E) >= 0)  // register edge: variable k's v2c is in this lane
+                v[E] = msg[P::row_reg(P0 + E)];
+            else if constexpr (SL >= 0)  // variable-indexed slot: row k's edge is at position (k + s) mod Z
+                v[E] = lds_rd_abs<SL * 256>(rot[P::T.shidx[P::inv_shift(P::row_shift(P0 + E))]]);
             else
                 v[E] = ext[P::ext_index(I, E)];
         });
     }
 
     template <int I, bool DEC, bool SLOW = false>
-    __device__ __forceinline__ void row(const Ctx &C, const Lane &L, const float (&v)[MAXDC], int &errs, float ninf, float pinf, uint32_t sgn, float alv) const {
-        constexpr int R = G::CHK_ROWS[P::R0 + I], P0 = G::ROW_PTR[R], DC = G::ROW_PTR[R + 1] - P0;
+    __device__ __forceinline__ void row(const Ctx &C, const Lane &L, const float (&v)[MAXDC], int &errs, float ninf, float pinf, uint32_t sgn, float alv) {
+        constexpr int R = P::chk_row(I), P0 = G::ROW_PTR[R], DC = G::ROW_PTR[R + 1] - P0;
         // an output is needed for a slot edge always, for a degree-1 edge only to take its decision
         auto needed = [](int e) constexpr { return DEC || G::ROW_SLOT[P0 + e] >= 0; };
         auto emit = [&](auto e, float o) {
             constexpr int E = decltype(e)::value, SL = G::ROW_SLOT[P0 + E];
-            if constexpr (SL >= 0) {
+            if constexpr (P::row_reg(P0 + E) >= 0) {
+                msg[P::row_reg(P0 + E)] = o;  // register edge: the c2v stays in this lane
+            } else if constexpr (SL >= 0) {
                 lds_wr_tid<SL * 256>(o);  // ds_write_addtid_b32: the slot entry of a row is slot[lane]
             } else if constexpr (DEC) {
                 if (C.direct_bits || C.ballots)  // degree-1 variable: APP = llr + c2v
-                    ext_decision(C, L, G::ROW_COL[P0 + E], 4 * G::ROW_SHIFT[P0 + E], v[E] + o, errs);
+                    ext_decision(C, L, G::ROW_COL[P0 + E], 4 * P::row_shift(P0 + E), v[E] + o, errs);
             }
         };
         if constexpr (ALGO == LDPC_ALGO_MINSUM && !SLOW && DC >= 2 && DC <= kDirectDc) {
@@ -1215,7 +1263,7 @@ struct FixedBody {
     }
 
     template <bool DEC>
-    __device__ __forceinline__ void check(const Ctx &C, const Lane &L, int &errs) const {
+    __device__ __forceinline__ void check(const Ctx &C, const Lane &L, int &errs) {
         if constexpr (ALGO == LDPC_ALGO_MINSUM) {
             if (__builtin_amdgcn_readfirstlane(*C.flag) != 0)
                 rows<DEC, true>(C, L, errs);
@@ -1227,7 +1275,7 @@ struct FixedBody {
     }
 
     template <bool DEC, bool SLOW>
-    __device__ __forceinline__ void rows(const Ctx &C, const Lane &L, int &errs) const {
+    __device__ __forceinline__ void rows(const Ctx &C, const Lane &L, int &errs) {
         float va[MAXDC], vb[MAXDC];
         addtid_begin(C.lds);
         const float ninf = opaque_sf(-INFINITY), pinf = opaque_sf(INFINITY);
@@ -1275,25 +1323,42 @@ struct FixedBody {
         float cs[MAXDV];  // DB <= J < DA: c_A[J]
     };
 
+    // the c2v of the edge at index X of COL_*: from msg[] (register edge: check k's output is in
+    // this lane) or from its check-indexed slot, read rotated
+    template <int X>
+    __device__ __forceinline__ float c2v_in() const {
+        if constexpr (P::col_reg(X) >= 0)
+            return msg[P::col_reg(X)];
+        else
+            return lds_rd_abs<G::COL_SLOT[X] * 256>(rot[P::T.shidx[P::col_shift(X)]]);
+    }
+    // the v2c of that edge: into msg[], or own-lane into its slot, which turns variable-indexed
+    // (ds_write_addtid_b32; every read of the slot was issued by load_task, before this store)
+    template <int X>
+    __device__ __forceinline__ void v2c_out(float o) {
+        if constexpr (P::col_reg(X) >= 0)
+            msg[P::col_reg(X)] = o;
+        else
+            lds_wr_tid<G::COL_SLOT[X] * 256>(o);
+    }
+
     template <int TK>
     __device__ __forceinline__ void load_task(const Ctx &C, TaskIn &in) const {
         using K = Task<TK>;
         sfor<K::DA>([&](auto jj) {
             constexpr int J = decltype(jj)::value;
-            constexpr int SA = G::COL_SLOT[K::PA + J], RA = P::T.shidx[G::COL_SHIFT[K::PA + J]];
             if constexpr (J < K::DB) {
-                constexpr int SB = G::COL_SLOT[K::PB + J], RB = P::T.shidx[G::COL_SHIFT[K::PB + J]];
-                in.cp[J].x = lds_rd_abs<SA * 256>(rot[RA]);
-                in.cp[J].y = lds_rd_abs<SB * 256>(rot[RB]);
+                in.cp[J].x = c2v_in<K::PA + J>();
+                in.cp[J].y = c2v_in<K::PB + J>();
             } else {
-                in.cs[J] = lds_rd_abs<SA * 256>(rot[RA]);
+                in.cs[J] = c2v_in<K::PA + J>();
             }
         });
     }
 
     template <int TK, bool DEC, bool WRITE>
     __device__ __forceinline__ void task(const Ctx &C, const Lane &L, const TaskIn &in, int &errs, bool &bad,
-                                         float &mz) const {
+                                         float &mz) {
         using K = Task<TK>;
         constexpr int DA = K::DA, DB = K::DB, LO = K::LO, HI = K::HI;
         f32x2 P2;
@@ -1332,18 +1397,16 @@ struct FixedBody {
         if constexpr (WRITE) {
             sfor<HI - LO>([&](auto q) {
                 constexpr int E = LO + decltype(q)::value;
-                // ds_write_addtid_b32: the v2c of variable t goes to position t, the slot turns
-                // variable-indexed (every read of it was issued by load_task, before this store)
-                constexpr int SA = G::COL_SLOT[K::PA + E];
+                // the v2c of variable t goes to position t of its slot, or stays in msg[] (v2c_out)
                 if constexpr (E < DB) {
-                    constexpr int SB = G::COL_SLOT[K::PB + E];
-                    lds_wr_tid<SA * 256>(acc2[E].x);
-                    lds_wr_tid<SB * 256>(acc2[E].y);
-                    // smallest |v2c| written: a zero sets the flag (v_minimum3: no canonicalising
-                    // v_max; a NaN here implies a non-finite APP, caught by `bad`)
+                    v2c_out<K::PA + E>(acc2[E].x);
+                    v2c_out<K::PB + E>(acc2[E].y);
+                    // smallest |v2c| written, register edges included: a zero sets the flag
+                    // (v_minimum3: no canonicalising v_max; a NaN here implies a non-finite APP,
+                    // caught by `bad`)
                     if constexpr (ALGO == LDPC_ALGO_MINSUM) mz = vmin(vmin(mz, fabsf(acc2[E].x)), fabsf(acc2[E].y));
                 } else {
-                    lds_wr_tid<SA * 256>(accA[E]);
+                    v2c_out<K::PA + E>(accA[E]);
                     if constexpr (ALGO == LDPC_ALGO_MINSUM) {
                         // two A-only outputs per v_minimum3
                         if constexpr ((E - (DB > LO ? DB : LO)) % 2 == 1)
@@ -1371,7 +1434,7 @@ struct FixedBody {
     }
 
     template <bool DEC, bool WRITE>
-    __device__ __forceinline__ void var(const Ctx &C, const Lane &L, int &errs) const {
+    __device__ __forceinline__ void var(const Ctx &C, const Lane &L, int &errs) {
         bool bad = false;
         float mz = INFINITY;
         if constexpr (P::NT > 0) {
@@ -1413,12 +1476,12 @@ struct FixedBody {
         int f = L.f, k = L.k;
         asm volatile("" : "+v"(f), "+v"(k));
         sfor<P::NR>([&](auto i) {
-            constexpr int R = G::CHK_ROWS[P::R0 + decltype(i)::value];
+            constexpr int R = P::chk_row(decltype(i)::value);
             constexpr int P0 = G::ROW_PTR[R], DC = G::ROW_PTR[R + 1] - P0;
             int p = 0;  // parity of check r*Z + k of frame f: xor of its variables' decisions
             sfor<DC>([&](auto e) {
                 constexpr int E = decltype(e)::value;
-                constexpr int COL = G::ROW_COL[P0 + E], S = G::ROW_SHIFT[P0 + E];
+                constexpr int COL = G::ROW_COL[P0 + E], S = P::row_shift(P0 + E);
                 p ^= (int)(C.words[COL] >> (f * G::Z + ((k + S) & (G::Z - 1))));
             });
             inv |= p;

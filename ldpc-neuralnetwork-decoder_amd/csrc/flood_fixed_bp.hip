@@ -1,5 +1,11 @@
 // flood_fixed_bp.hip -- flood_fixed_kernel instances for sum-product (BP) (compile-time schedules of the reference's codes).
 // Split out of flood.hip so that the kernel families compile in parallel.
+// The BP instances run without register edges (flood_dev.hpp LDPC_REG_EDGES): their check phase is
+// bound by the tanh / atanh VALU work, not by LDS, and with msg[] bp-z32 measured 1.7 % slower
+// (profiles/r10).  -DLDPC_REG_EDGES=1 builds them with it (tests pass either way).
+#ifndef LDPC_REG_EDGES
+#define LDPC_REG_EDGES 0
+#endif
 #include "flood_host.hpp"
 
 namespace ldpc {

@@ -21,6 +21,14 @@ CODES = [("BG2_Z4", os.path.join(ROOT, "codes", "NR_2_0_4.txt"), 4),
          ("BG2_Z32", os.path.join(ROOT, "codes", "NR_2_0_32.txt"), 32)]
 W = 4
 DIRECT_DC = 6  # the default of LDPC_DIRECT_DC in csrc/flood_dev.hpp
+# Register edges (RE_* arrays, LDPC_REG_EDGES in csrc/flood_dev.hpp): at most this many messages
+# per wave stay in VGPRs.  The largest value at which every min-sum and BP instance of both codes
+# keeps its register budget (128 VGPRs without early stop, 168 with, no scratch).
+REG_EDGE_CAP = 8
+# modelled LDS cycles a register edge saves: the check phase's per-edge term of the row costs, and
+# the read and the write of var_task_cost
+CHK_EDGE_LDS = 2.0
+VAR_EDGE_LDS = 18.12
 
 
 def load(path):
@@ -83,7 +91,132 @@ def arr(name, vals):
     return f"    static constexpr int {name}[{len(vals)}] = {{{body}}};\n"
 
 
-def gen(name, base, z):
+def reg_edge_schedule(blocks, z, mb, dv, row_ptr, rcost, sched, cap):
+    """The register-edge schedule (RE_* arrays).
+
+    Checks are anonymous: relabelling the Z checks of block row r by an offset rho_r turns every
+    shift s of the row into (s + rho_r) mod Z and leaves the code, every variable's ascending
+    block-row order and every row's column order as they are.  An edge whose normalised shift is 0
+    joins check lane k to variable lane k of the same frame; when its row and its column are also
+    on the same wave (and the column has a slot, degree >= 2) its message can stay in one VGPR of
+    that lane for the whole decode.
+
+    Chooses rho_r and the wave of every row for the given variable schedule `sched`: most
+    register edges (at most `cap` per wave), then the smallest modelled makespan of both phases
+    (rcost and var_task_cost, minus the LDS terms of register edges), then the fewest distinct
+    rotations (rot[] VGPRs; largest wave first, then the sum).  Restricted LPT start, then
+    single-row changes and wave swaps of two rows while the key improves: deterministic.
+    Returns (rho, rows per wave, register edges per wave as block indices in row order)."""
+    colwave = {}
+    for w, p in enumerate(sched):
+        for a, b, _, _ in p:
+            colwave[a] = w
+            if b >= 0:
+                colwave[b] = w
+    vbase = [sum(var_task_cost(dv[a], dv[b] if b >= 0 else 0, lo, hi) for a, b, lo, hi in p) for p in sched]
+    edges = [list(range(row_ptr[r], row_ptr[r + 1])) for r in range(mb)]
+    slot_edges = [[i for i in edges[r] if dv[blocks[i][1]] >= 2] for r in range(mb)]
+    rhos = [sorted({0} | {(-blocks[i][2]) % z for i in slot_edges[r]}) for r in range(mb)]
+    elig = {(r, rho, w): [i for i in slot_edges[r] if (blocks[i][2] + rho) % z == 0 and colwave[blocks[i][1]] == w]
+            for r in range(mb) for rho in rhos[r] for w in range(W)}
+    col_edges = [[i for i in range(len(blocks)) if dv[blocks[i][1]] >= 2 and colwave[blocks[i][1]] == w]
+                 for w in range(W)]
+
+    def regs(rho, wave):
+        reg = [[] for _ in range(W)]
+        for r in range(mb):
+            reg[wave[r]] += elig[(r, rho[r], wave[r])]
+        return [x[:cap] for x in reg]
+
+    def loads(wave, reg):
+        chk = [0.0] * W
+        for r in range(mb):
+            chk[wave[r]] += rcost[r]
+        chk = [chk[w] - CHK_EDGE_LDS * len(reg[w]) for w in range(W)]
+        var = [vbase[w] - 2 * VAR_EDGE_LDS * len(reg[w]) for w in range(W)]
+        return chk, var
+
+    def rotations(rho, wave, reg):
+        out = []
+        for w in range(W):
+            inreg = set(reg[w])
+            s = {(blocks[i][2] + rho[blocks[i][0]]) % z for i in col_edges[w] if i not in inreg}
+            for r in range(mb):
+                if wave[r] == w:
+                    s |= {(-(blocks[i][2] + rho[r])) % z for i in slot_edges[r] if i not in inreg}
+            out.append(len(s))
+        return out
+
+    def key2(rho, wave):
+        reg = regs(rho, wave)
+        chk, var = loads(wave, reg)
+        return (-sum(len(x) for x in reg), round(max(chk) + max(var), 6))
+
+    def better(rho, wave, cur):
+        """full key of (rho, wave) if it beats cur, else None; rotations only counted on a tie"""
+        k = key2(rho, wave)
+        if k > cur[:2]:
+            return None
+        rot = rotations(rho, wave, regs(rho, wave))
+        full = k + (max(rot), sum(rot))
+        return full if full < cur else None
+
+    # restricted LPT: heaviest row first, onto the lightest wave that gives it a register edge
+    rho, wave = [0] * mb, [-1] * mb
+    load, used = [0.0] * W, [0] * W
+    for r in sorted(range(mb), key=lambda q: -rcost[q]):
+        opts = [(load[w], -len(elig[(r, h, w)]), w, h) for w in range(W) for h in rhos[r]
+                if elig[(r, h, w)] and used[w] < cap]
+        if opts:
+            _, n, w, h = min(opts)
+        else:
+            w, h, n = min(range(W), key=lambda j: load[j]), 0, 0
+        rho[r], wave[r] = h, w
+        load[w] += rcost[r]
+        used[w] += -n
+    k0 = key2(rho, wave)
+    rot0 = rotations(rho, wave, regs(rho, wave))
+    cur = k0 + (max(rot0), sum(rot0))
+    improved = True
+    while improved:
+        improved = False
+        for r in range(mb):
+            keep = (rho[r], wave[r])
+            best = None
+            for w in range(W):
+                for h in rhos[r]:
+                    if (h, w) == keep:
+                        continue
+                    rho[r], wave[r] = h, w
+                    k = better(rho, wave, best[0] if best else cur)
+                    if k is not None:
+                        best = (k, h, w)
+            rho[r], wave[r] = keep
+            if best:
+                cur, rho[r], wave[r] = best
+                improved = True
+        for r in range(mb):
+            for q in range(r + 1, mb):
+                if wave[r] == wave[q]:
+                    continue
+                keep = (rho[r], wave[r], rho[q], wave[q])
+                wave[r], wave[q] = wave[q], wave[r]
+                # each row's own best offset on its new wave (most eligible edges, smallest first)
+                rho[r] = min(rhos[r], key=lambda h: (-len(elig[(r, h, wave[r])]), h))
+                rho[q] = min(rhos[q], key=lambda h: (-len(elig[(q, h, wave[q])]), h))
+                k = better(rho, wave, cur)
+                if k is not None:
+                    cur = k
+                    improved = True
+                else:
+                    rho[r], wave[r], rho[q], wave[q] = keep
+    reg = regs(rho, wave)
+    chk, var = loads(wave, reg)
+    info = {"chk": chk, "var": var, "rot": rotations(rho, wave, reg)}
+    return rho, [[r for r in range(mb) if wave[r] == w] for w in range(W)], reg, info
+
+
+def gen(name, base, z, reg_edges=True, cap=None, report=None):
     mb, nb = len(base), len(base[0])
     blocks = [(r, c, base[r][c] % z) for r in range(mb) for c in range(nb) if base[r][c] >= 0]
     dv = [0] * nb
@@ -163,6 +296,33 @@ def gen(name, base, z):
         s += arr(f"{pre}_HI", [t[3] for t in tl])
     s += arr("BW_PTR", bp)
     s += arr("BW_COLS", bl)
+    if reg_edges:
+        # the register-edge schedule beside the one above (reg_edge_schedule): offsets, normalised
+        # shifts in the order of ROW_SHIFT / COL_SHIFT, per edge the index into the wave's msg[]
+        # (-1: the message lives in its LDS slot), rows per wave.  Columns stay on VT's waves.
+        cap = REG_EDGE_CAP if cap is None else cap
+        rho, rchk, reg, info = reg_edge_schedule(blocks, z, mb, dv, row_ptr, rcost, vt_pair, cap)
+        rshift = [(b[2] + rho[b[0]]) % z for b in blocks]
+        ridx = [-1] * len(blocks)
+        for w in range(W):
+            for x, i in enumerate(reg[w]):
+                ridx[i] = x
+        rp, rl = flat(rchk)
+        s += f"    static constexpr int RE_CAP = {cap};\n"
+        s += arr("RE_RHO", rho)
+        s += arr("RE_ROW_SHIFT", rshift)
+        s += arr("RE_COL_SHIFT", [rshift[i] for c in range(nb) for i in col_blocks[c]])
+        s += arr("RE_ROW_REG", ridx)
+        s += arr("RE_COL_REG", [ridx[i] for c in range(nb) for i in col_blocks[c]])
+        s += arr("RE_NREG", [len(x) for x in reg])
+        s += arr("RE_CHK_PTR", rp)
+        s += arr("RE_CHK_ROWS", rl)
+        if report is not None:
+            c = dict(zip(rows, rcost))
+            report[name] = dict(info, rho=rho, nreg=[len(x) for x in reg], rows=rchk,
+                                chk_old=[sum(c[r] for r in p) for p in chk],
+                                var_old=[sum(var_task_cost(dv[a], dv[b] if b >= 0 else 0, lo, hi)
+                                             for a, b, lo, hi in p) for p in vt_pair])
     s += "};\n\n"
     return s
 
@@ -263,13 +423,26 @@ def var_schedule(vcols, dv, w, pairs=True):
     return [sorted(p) for p in best[1]]
 
 
-def main(out):
+def header_text(reg_edges=True, cap=None, report=None):
+    """The header's text; reg_edges=False leaves the RE_* arrays out (the schedule before them)."""
     text = ("// GENERATED by tools/gen_fixed_codes.py from codes/NR_2_0_{4,32}.txt -- do not edit.\n"
             "// Compile-time flooding schedules for the two codes the reference ships (see that script).\n"
             "#pragma once\n\nnamespace ldpc {\nnamespace fixed {\n\n")
     for name, path, z in CODES:
-        text += gen(name, load(path), z)
+        text += gen(name, load(path), z, reg_edges, cap, report)
     text += "}  // namespace fixed\n}  // namespace ldpc\n"
+    return text
+
+
+def main(out):
+    # LDPC_REG_EDGE_CAP: a smaller cap for A/B builds (tools/build_variant.sh on a copy of the tree)
+    cap = int(os.environ["LDPC_REG_EDGE_CAP"]) if os.environ.get("LDPC_REG_EDGE_CAP") else None
+    report = {}
+    text = header_text(True, cap, report)
+    if os.environ.get("LDPC_GEN_REPORT"):
+        for name, r in report.items():
+            print(name, {k: ([round(x, 1) for x in v] if k in ("chk", "var", "chk_old", "var_old") else v)
+                         for k, v in r.items()}, file=sys.stderr)
     os.makedirs(os.path.dirname(out), exist_ok=True)
     old = open(out).read() if os.path.exists(out) else None
     if old != text:
