@@ -86,7 +86,11 @@ int ldpc_graph_edges(const ldpc_graph *g, int32_t *h_edge_chk, int32_t *h_edge_v
  *   (comparative_evaluation.py:133); counting is fused into the decoder's epilogue.
  * d_work / work_bytes: scratch of ldpc_flood_workspace_size(...) bytes, required for
  *   LDPC_ES_BATCH and whenever d_counters (or d_batch_iters with LDPC_ES_FRAME) is given: the
- *   counters are reduced through per-workgroup rows, not same-address atomics.
+ *   counters are reduced through per-workgroup rows, not same-address atomics.  Give it always
+ *   where speed matters: with it, min-sum on the reference's two codes (LDPC_ES_OFF / LDPC_ES_FRAME)
+ *   runs a kernel that holds the fast check update only; a group of frames that meets a NaN or an
+ *   infinity leaves that kernel, is listed in the workspace and is decoded again by the exact
+ *   table-driven kernel in a second launch on the same stream (same results, no host round trip).
  * LDPC_ES_BATCH runs as passes on the stream (first all-valid iteration per workgroup, then the
  *   batch's candidate T, then -- only if some frame is invalid at T -- the exhaustive search);
  *   it never synchronises with the host.
@@ -118,6 +122,12 @@ int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_llr, int64_t
                       float alpha, int early_stop, int out_dtype, void *d_bits, int32_t *d_iters,
                       int32_t *d_batch_iters, uint64_t *d_counters, void *d_work,
                       int64_t work_bytes, void *stream);
+/* How many frame groups (64 / Z frames each: group i holds frames i * 64 / Z ..) the last
+ * ldpc_flood_decode with these arguments and this d_work decoded a second time (see d_work above),
+ * and, when h_groups is given (room for ceil(B / (64 / Z)) entries), which, in no particular order.
+ * Synchronises the stream.  LDPC_EUNSUPPORTED for a decode that keeps no such list. */
+int ldpc_flood_redo_count(const ldpc_graph *g, int algo, int64_t B, int max_iter, int early_stop,
+                          const void *d_work, void *stream, int32_t *h_count, int32_t *h_groups);
 
 /* ------------------------------------------------------------------ hybrid min-sum
  * Replaces: CustomMinSumMessageGNNDecoder.forward (models/message_gnn_decoder.py:1167-1251) with

@@ -137,6 +137,31 @@ __global__ __launch_bounds__(512) void batch_emit_kernel(FloodTables T, const ui
 
 __global__ void fill_i32_kernel(int32_t *p, int32_t v) { *p = v; }
 
+// Second launch behind a bail-out instance of flood_fixed_kernel (flood_dev.hpp Body::kBail): the
+// groups on its redo list are decoded again from their LLRs by the table-driven update, which is
+// bit-identical and exact for every value, and get their bits, iteration counts and counter rows
+// here.  A fixed small grid strides over the list; with an empty list (no non-finite value in the
+// batch: always, on real data) every workgroup leaves at once, so the host never has to look.
+template <int ES>
+__global__ __launch_bounds__(512) void flood_redo_kernel(FloodTables T, const float *__restrict__ llr, int64_t B,
+                                                         int max_iter, float alpha, int out_dtype,
+                                                         void *__restrict__ bits, Outs O,
+                                                         const uint32_t *__restrict__ redo) {
+    static_assert(ES == LDPC_ES_OFF || ES == LDPC_ES_FRAME, "flood_drive returns early in the batch-stop passes");
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const uint32_t n = __builtin_amdgcn_readfirstlane(redo[0]);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const int group = __builtin_amdgcn_readfirstlane(redo[1 + i]);
+        const Lane L = make_lane(T, llr, B, group);
+        Ctx C;
+        init_ctx(C, T, lds, alpha, out_dtype, bits);
+        GenericBody<LDPC_ALGO_MINSUM> body{__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6)};
+        flood_drive<ES>(body, C, L, B, max_iter, O, EsWs{});
+        __syncthreads();  // the next group's init writes the LDS this one's epilogue reads
+    }
+}
+constexpr unsigned kRedoGrid = 256;  // one workgroup per CU
+
 
 int reduce_counter_rows(const uint32_t *partials, int64_t nwg, uint64_t *counters, int32_t *batch_iters,
                         const int32_t *gate, hipStream_t s) {
@@ -155,10 +180,11 @@ size_t flood_lds_bytes(const ldpc_graph *g, int es) {
     return std::max<size_t>(b, 2 * 64 * (size_t)g->ft.W * sizeof(uint32_t));
 }
 
-// Workspace: [counter rows: nwg x kPartRow uint32] then, for LDPC_ES_BATCH, the EsWs arrays.
-// base == nullptr only sizes it.
+// Workspace: [counter rows: nwg x kPartRow uint32] [redo list: count, nwg x uint32] then, for
+// LDPC_ES_BATCH, the EsWs arrays.  base == nullptr only sizes it.
 struct FloodWs {
     uint32_t *partials;
+    uint32_t *redo;
     EsWs es;
     uint32_t *all;
     int64_t bytes;
@@ -171,6 +197,7 @@ FloodWs flood_ws(const ldpc_graph *g, int64_t B, int max_iter, int early_stop, v
     size_t off = 0;
     auto take = [&](size_t n) { char *q = p ? p + off : nullptr; off += align256(n); return q; };
     w.partials = reinterpret_cast<uint32_t *>(take((size_t)nwg * kPartRow * 4));
+    w.redo = reinterpret_cast<uint32_t *>(take((size_t)(nwg + 1) * 4));
     if (early_stop == LDPC_ES_BATCH) {
         EsWs &e = w.es;
         e.nvw = (max_iter + 31) / 32;
@@ -192,16 +219,39 @@ bool use_stream(const ldpc_graph *g, int es) {
     return e && std::atoi(e) != 0;
 }
 
+// the decodes that run a bail-out instance and the redo launch behind it
+bool has_redo(const ldpc_graph *g, int algo, int es) {
+    return g->fixed_id != 0 && algo == LDPC_ALGO_MINSUM && (es == LDPC_ES_OFF || es == LDPC_ES_FRAME);
+}
+
+// redo (has_redo decodes, NULL without a workspace): the redo list of FloodWs
 template <int ALGO, int ES>
 int launch_flood(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int out_dtype,
-                 void *bits, const Outs &O, const EsWs &W, hipStream_t s) {
+                 void *bits, const Outs &O, const EsWs &W, hipStream_t s, uint32_t *redo = nullptr) {
     const size_t lds = flood_lds_bytes(g, ES);
     const int64_t nwg = (B + g->FG - 1) / g->FG;
     if (g->fixed_id != 0) {  // compile-time schedules: their own translation units
         const dim3 grid((unsigned)nwg), block(64 * g->ft.W);
+        if constexpr (ALGO == LDPC_ALGO_MINSUM && (ES == LDPC_ES_OFF || ES == LDPC_ES_FRAME)) {
+            if (redo) {
+                LDPC_HIP(hipMemsetAsync(redo, 0, sizeof(uint32_t), s));
+                int rc = launch_fixed_minsum(g->fixed_id, ES, grid, block, lds, s, g->ft, llr, B, max_iter, alpha,
+                                             out_dtype, bits, O, W, redo);
+                if (rc != LDPC_OK) return rc;
+                auto again = flood_redo_kernel<ES>;
+                LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(again),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                Outs Or = O;
+                Or.timeline = nullptr;
+                hipLaunchKernelGGL(again, dim3((unsigned)std::min<int64_t>(nwg, kRedoGrid)), block, lds, s, g->ft, llr,
+                                   B, max_iter, alpha, out_dtype, bits, Or, (const uint32_t *)redo);
+                LDPC_CHECK_LAUNCH("flood_redo_kernel");
+                return LDPC_OK;
+            }
+        }
         return ALGO == LDPC_ALGO_MINSUM
                    ? launch_fixed_minsum(g->fixed_id, ES, grid, block, lds, s, g->ft, llr, B, max_iter, alpha,
-                                         out_dtype, bits, O, W)
+                                         out_dtype, bits, O, W, nullptr)
                    : launch_fixed_bp(g->fixed_id, ES, grid, block, lds, s, g->ft, llr, B, max_iter, alpha,
                                      out_dtype, bits, O, W);
     }
@@ -238,7 +288,7 @@ int run_flood(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, fl
         LDPC_HIP(hipMemsetAsync(tl, 0, tl_n * 8, s));
         Outs Ot = O;
         Ot.timeline = tl;
-        int rc = launch_flood<ALGO, LDPC_ES_OFF>(g, llr, B, max_iter, alpha, out_dtype, bits, Ot, EsWs{}, s);
+        int rc = launch_flood<ALGO, LDPC_ES_OFF>(g, llr, B, max_iter, alpha, out_dtype, bits, Ot, EsWs{}, s, ws.redo);
         if (const char *path = std::getenv("LDPC_TIMELINE_OUT")) {
             std::vector<uint64_t> h(tl_n);
             LDPC_HIP(hipStreamSynchronize(s));
@@ -251,13 +301,13 @@ int run_flood(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, fl
             }
         }
 #else
-        int rc = launch_flood<ALGO, LDPC_ES_OFF>(g, llr, B, max_iter, alpha, out_dtype, bits, O, EsWs{}, s);
+        int rc = launch_flood<ALGO, LDPC_ES_OFF>(g, llr, B, max_iter, alpha, out_dtype, bits, O, EsWs{}, s, ws.redo);
 #endif
         // ES off: every frame ran max_iter (batch_iters was set before the launch)
         return rc != LDPC_OK ? rc : reduce_rows(g, B, ws.partials, counters, nullptr, nullptr, s);
     }
     if (es == LDPC_ES_FRAME) {
-        int rc = launch_flood<ALGO, LDPC_ES_FRAME>(g, llr, B, max_iter, alpha, out_dtype, bits, O, EsWs{}, s);
+        int rc = launch_flood<ALGO, LDPC_ES_FRAME>(g, llr, B, max_iter, alpha, out_dtype, bits, O, EsWs{}, s, ws.redo);
         return rc != LDPC_OK ? rc : reduce_rows(g, B, ws.partials, counters, batch_iters, nullptr, s);
     }
     const EsWs &W = ws.es;
@@ -333,10 +383,11 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
     if (streaming && (g->max_dv > kStreamMaxDeg || g->max_dc > kStreamMaxDeg))
         return fail(LDPC_EUNSUPPORTED, "streaming decoder: node degree above " + std::to_string(kStreamMaxDeg));
     // scratch is needed by the streaming decoder, the batch-global stop and any counter output
-    if (streaming || early_stop == LDPC_ES_BATCH || d_counters || (d_batch_iters && early_stop == LDPC_ES_FRAME)) {
-        const int64_t need = ldpc_flood_workspace_size(g, B, max_iter, early_stop);
-        if (!d_work || work_bytes < need)
+    const int64_t need = ldpc_flood_workspace_size(g, B, max_iter, early_stop);
+    if (!d_work || work_bytes < need) {
+        if (streaming || early_stop == LDPC_ES_BATCH || d_counters || (d_batch_iters && early_stop == LDPC_ES_FRAME))
             return fail(LDPC_EINVAL, "workspace too small: need " + std::to_string(need) + " bytes");
+        d_work = nullptr;  // not required: the fixed min-sum kernels then keep their exact check update inside
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (d_batch_iters && early_stop == LDPC_ES_OFF) {
@@ -357,6 +408,24 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
                                              d_counters, d_batch_iters, d_work, s)
                : run_flood<LDPC_ALGO_BP>(g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits, d_iters,
                                          d_counters, d_batch_iters, d_work, s);
+}
+
+extern "C" int ldpc_flood_redo_count(const ldpc_graph *g, int algo, int64_t B, int max_iter, int early_stop,
+                                     const void *d_work, void *stream, int32_t *h_count, int32_t *h_groups) {
+    if (!g || !d_work || !h_count || B <= 0 || max_iter < 1) return fail(LDPC_EINVAL, "bad arguments");
+    if (use_stream(g, early_stop) || !has_redo(g, algo, early_stop))
+        return fail(LDPC_EUNSUPPORTED, "this decode keeps no redo list (min-sum on a compile-time schedule, "
+                                       "LDPC_ES_OFF or LDPC_ES_FRAME, only)");
+    const FloodWs ws = flood_ws(g, B, max_iter, early_stop, const_cast<void *>(d_work));
+    uint32_t n = 0;
+    LDPC_HIP(hipMemcpyAsync(&n, ws.redo, sizeof n, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
+    LDPC_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    *h_count = (int32_t)n;
+    if (h_groups && n > 0) {
+        if ((int64_t)n > (B + g->FG - 1) / g->FG) return fail(LDPC_EINVAL, "d_work holds no redo list of this decode");
+        LDPC_HIP(hipMemcpy(h_groups, ws.redo + 1, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return LDPC_OK;
 }
 
 extern "C" int64_t ldpc_custom_minsum_workspace_size(const ldpc_graph *g, int64_t B) {

@@ -103,6 +103,7 @@ struct Lane {
     int zmask4;    // 4 * Z - 1 (Z is a power of two)
     int z4;        // 4 * Z
     bool valid;    // the lane's frame exists
+    int group;     // the workgroup's lane vector: frames group * FG ..  (the block index, except in a redo)
     int64_t frame;
     const char *llr_row;  // this lane's frame row (frame 0 for lanes without a frame)
     // byte offset inside a slot of the message on a block with byte shift s4, seen from the
@@ -357,6 +358,7 @@ struct Ctx {
     char *lds;
     uint64_t *words;  // ES: Nb decision ballots + 1 invalid-lane word (in LDS)
     uint32_t *flag;   // LDS: sticky "a v2c may be NaN" flag of the fixed kernel's fast check path
+    uint32_t *redo;   // bail-out instances (Body::kBail): [0] count, [1 ..] groups to decode again
     float alpha;
     int out_dtype;
     void *bits;
@@ -686,8 +688,9 @@ __device__ __forceinline__ void reduce_counters(void *lds, const Lane &L, int er
     }
 }
 
-__device__ __forceinline__ Lane make_lane(const FloodTables &T, const float *llr, int64_t B) {
+__device__ __forceinline__ Lane make_lane(const FloodTables &T, const float *llr, int64_t B, int group) {
     Lane L;
+    L.group = group;
     L.lane = threadIdx.x & 63;
     const int lz = __builtin_ctz((unsigned)T.Z);  // Z is a power of two
     L.f = L.lane >> lz;
@@ -697,10 +700,13 @@ __device__ __forceinline__ Lane make_lane(const FloodTables &T, const float *llr
     L.k4 = 4 * L.k;
     L.z4 = 4 * T.Z;
     L.zmask4 = 4 * T.Z - 1;
-    L.frame = (int64_t)blockIdx.x * T.FG + L.f;
+    L.frame = (int64_t)group * T.FG + L.f;
     L.valid = L.frame < B;
     L.llr_row = reinterpret_cast<const char *>(llr ? llr + (L.valid ? L.frame : 0) * (int64_t)T.N : nullptr);
     return L;
+}
+__device__ __forceinline__ Lane make_lane(const FloodTables &T, const float *llr, int64_t B) {
+    return make_lane(T, llr, B, (int)blockIdx.x);
 }
 
 // ---------------------------------------------------------------- early stop: internal modes
@@ -739,7 +745,7 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int FG = C.T.FG, Nb = C.T.Nb, Z = C.T.Z;
-    const int nf = (int)min<int64_t>((int64_t)FG, B - (int64_t)blockIdx.x * FG);
+    const int nf = (int)min<int64_t>((int64_t)FG, B - (int64_t)L.group * FG);
     const uint64_t exist = nf >= 64 ? ~0ull : ((1ull << nf) - 1ull);
     int errs = 0;
     if constexpr (ES == LDPC_ES_BATCH) {
@@ -747,10 +753,10 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
     }
     if constexpr (ES == ES_P2) {
         const int T = __builtin_amdgcn_readfirstlane(W.ctl[0]);
-        if (__builtin_amdgcn_readfirstlane(W.twg[blockIdx.x]) == T) {
-            emit_from_words(C, L, W.cand + (int64_t)blockIdx.x * Nb, exist, wave, errs);
+        if (__builtin_amdgcn_readfirstlane(W.twg[L.group]) == T) {
+            emit_from_words(C, L, W.cand + (int64_t)L.group * Nb, exist, wave, errs);
             if (O.iters_out && L.valid && L.k == 0) O.iters_out[L.frame] = T;
-            reduce_counters(C.lds, L, errs, T, nf, Z, O.partials + (int64_t)blockIdx.x * kPartRow);
+            reduce_counters(C.lds, L, errs, T, nf, Z, O.partials + (int64_t)L.group * kPartRow);
             return;
         }
         max_iter = T;
@@ -783,6 +789,17 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
         const bool last = it == max_iter - 1;
         C.direct_bits = (ES == LDPC_ES_OFF || ES == ES_P2) && last;
         C.ballots = ES == LDPC_ES_BATCH || ES == LDPC_ES_FRAME || ES == ES_P1 || (ES == ES_P2 && last);
+        if constexpr (Body::kBail) {
+            // Bail-out instances hold the fast check update only.  The sticky flag (a non-finite
+            // LLR or APP: a message may be NaN) is read here by every wave after a barrier and
+            // written only between the next two, so the branch is workgroup-uniform: the group is
+            // appended to the redo list and decoded again, from its LLRs, by flood_redo_kernel.
+            // Whatever this workgroup has emitted so far is rewritten there; no counter row yet.
+            if (__builtin_amdgcn_readfirstlane(*C.flag) != 0) {
+                if (tid == 0) C.redo[1 + atomicAdd(C.redo, 1u)] = (uint32_t)L.group;
+                return;
+            }
+        }
         // decisions are taken only in the iterations that need them (DEC = true), so the other
         // iterations carry no decision code at all
         if (kEvery || last)
@@ -812,7 +829,7 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
             if constexpr (ES == LDPC_ES_BATCH) {
                 if (L.valid && L.k == 0 && ((vmask >> L.f) & 1ull))
                     W.valid[L.frame * W.nvw + (it >> 5)] |= 1u << (it & 31);
-                uint64_t *dst = W.words + ((int64_t)blockIdx.x * max_iter + it) * Nb;
+                uint64_t *dst = W.words + ((int64_t)L.group * max_iter + it) * Nb;
                 for (int c = tid; c < Nb; c += blockDim.x) dst[c] = C.words[c];
             } else if constexpr (ES == LDPC_ES_FRAME) {
                 const uint64_t newly = vmask & ~done;
@@ -826,10 +843,10 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
             } else if constexpr (ES == ES_P1) {
                 stop = vmask == exist || last;
                 if (stop) {
-                    uint64_t *dst = W.cand + (int64_t)blockIdx.x * Nb;
+                    uint64_t *dst = W.cand + (int64_t)L.group * Nb;
                     for (int c = tid; c < Nb; c += blockDim.x) dst[c] = C.words[c];
                     if (tid == 0) {
-                        W.twg[blockIdx.x] = it + 1;
+                        W.twg[L.group] = it + 1;
                         atomicMax(&W.ctl[0], it + 1);
                     }
                 }
@@ -851,13 +868,14 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
         if (O.iters_out && L.valid && L.k == 0) O.iters_out[L.frame] = max_iter;
     }
     if constexpr (ES == LDPC_ES_OFF || ES == LDPC_ES_FRAME) {
-        if (O.partials) reduce_counters(C.lds, L, errs, my_iters, nf, Z, O.partials + (int64_t)blockIdx.x * kPartRow);
+        if (O.partials) reduce_counters(C.lds, L, errs, my_iters, nf, Z, O.partials + (int64_t)L.group * kPartRow);
     }
-    if constexpr (ES == ES_P2) reduce_counters(C.lds, L, errs, max_iter, nf, Z, O.partials + (int64_t)blockIdx.x * kPartRow);
+    if constexpr (ES == ES_P2) reduce_counters(C.lds, L, errs, max_iter, nf, Z, O.partials + (int64_t)L.group * kPartRow);
 }
 
 template <int ALGO>
 struct GenericBody {
+    static constexpr bool kBail = false;  // its check update handles every value
     int wave;
     __device__ __forceinline__ void init(Ctx &C, const Lane &L) { init_phase(C, L, wave); }
     template <bool DEC>
@@ -880,6 +898,7 @@ __device__ __forceinline__ void init_ctx(Ctx &C, const FloodTables &T, char *lds
     C.bits = bits;
     C.direct_bits = false;
     C.ballots = false;
+    C.redo = nullptr;
 }
 
 }  // namespace
@@ -965,18 +984,38 @@ namespace {
 #error "LDPC_REG_EDGES=1 needs the paired variable schedule (LDPC_VAR_PAIRS=1)"
 #endif
 
-// per-wave compile-time plan
-template <class G, int WV>
+// Instances that keep the exact slow check update in the kernel (rows<DEC, true>: the batch-stop
+// passes, and every min-sum instance when the caller gives no workspace for a redo list) hold both
+// forms' registers at once, so they keep at most this many of a wave's register edges: the
+// largest values at which none of them spills VGPRs -- one for the instances with
+// early stop (3 workgroups per CU, 168 VGPRs: every edge fits), one for those without (4 per CU,
+// 128 VGPRs).
+#ifndef LDPC_SLOW_REG_EDGES
+#define LDPC_SLOW_REG_EDGES 16
+#endif
+#ifndef LDPC_SLOW_REG_EDGES_OFF
+#define LDPC_SLOW_REG_EDGES_OFF 6
+#endif
+constexpr int kAllRegEdges = 1 << 20;
+template <int ES, bool BAIL>
+constexpr int reg_edge_cap() {
+    return BAIL ? kAllRegEdges : (ES == LDPC_ES_OFF ? LDPC_SLOW_REG_EDGES_OFF : LDPC_SLOW_REG_EDGES);
+}
+
+// per-wave compile-time plan; CAP: the first CAP register edges of the wave's msg[] order are kept,
+// an edge past it is the shift-0 slot edge it still is (its slot stays allocated)
+template <class G, int WV, int CAP>
 struct FxPlan {
 #if LDPC_REG_EDGES
-    static constexpr int R0 = G::RE_CHK_PTR[WV], NR = G::RE_CHK_PTR[WV + 1] - R0, NREG = G::RE_NREG[WV];
+    static constexpr int R0 = G::RE_CHK_PTR[WV], NR = G::RE_CHK_PTR[WV + 1] - R0;
+    static constexpr int NREG = G::RE_NREG[WV] < CAP ? G::RE_NREG[WV] : CAP;
     static constexpr int chk_row(int i) { return G::RE_CHK_ROWS[R0 + i]; }
     // by edge index in row order (ROW_*) / in column order (COL_*): the normalised shift, and the
     // edge's index into msg[] (-1: the message lives in its LDS slot)
     static constexpr int row_shift(int e) { return G::RE_ROW_SHIFT[e]; }
     static constexpr int col_shift(int j) { return G::RE_COL_SHIFT[j]; }
-    static constexpr int row_reg(int e) { return G::RE_ROW_REG[e]; }
-    static constexpr int col_reg(int j) { return G::RE_COL_REG[j]; }
+    static constexpr int row_reg(int e) { return G::RE_ROW_REG[e] < CAP ? G::RE_ROW_REG[e] : -1; }
+    static constexpr int col_reg(int j) { return G::RE_COL_REG[j] < CAP ? G::RE_COL_REG[j] : -1; }
 #else
     static constexpr int R0 = G::CHK_PTR[WV], NR = G::CHK_PTR[WV + 1] - R0, NREG = 0;
     static constexpr int chk_row(int i) { return G::CHK_ROWS[R0 + i]; }
@@ -1063,7 +1102,8 @@ static_assert(kDirectDc >= 0 && kDirectDc <= 6, "direct_row is written out for d
 
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
 
-// Output E of a min-sum row of degree DC with no zero and no NaN message, without the two minima:
+// Output E of a min-sum row of degree DC with no NaN message, without the two minima (a zero
+// message gives the reference's outputs up to the sign of a zero, see FixedBody::row):
 //   c2v_E = (xor of the other inputs' sign bits) ^ (alpha * min of the other inputs' magnitudes)
 // The excluded minimum |x_E| == m1 ? m2 : m1 of the select form is this minimum as a float (a tie
 // at m1 puts m1 in m2), the product is the same single multiply, and the sign is the same xor: bit
@@ -1100,9 +1140,13 @@ __device__ __forceinline__ float direct_row(const float (&v)[CAP], const float (
     }
 }
 
-template <class G, int ALGO, int WV>
+// BAIL: the min-sum instance holds the fast check update only and leaves the decode when the sticky
+// flag is up (flood_drive, Body::kBail); otherwise check() branches to the exact form in the kernel.
+template <class G, int ALGO, int WV, bool BAIL, int CAP>
 struct FixedBody {
-    using P = FxPlan<G, WV>;
+    static_assert(!BAIL || ALGO == LDPC_ALGO_MINSUM, "only min-sum has a fast and an exact check update");
+    static constexpr bool kBail = BAIL;
+    using P = FxPlan<G, WV, CAP>;
     static constexpr int ZM4 = 4 * G::Z - 1;
     static constexpr int NEXT = P::T.next > 0 ? P::T.next : 1;
     static constexpr int NCOL = P::NC > 0 ? P::NC : 1;
@@ -1124,7 +1168,7 @@ struct FixedBody {
                 if constexpr (G::ROW_SLOT[P0 + E] < 0) {
                     constexpr int X = P::ext_index(I, E), COL = G::ROW_COL[P0 + E], S4 = 4 * P::row_shift(P0 + E);
                     ext[X] = L.llr_at(COL * 4 * G::Z + ((L.k4 + S4) & ZM4));
-                    nan |= is_zero_sign(ext[X]);  // zero or NaN: the sticky flag (see check())
+                    nan |= !(fabsf(ext[X]) < INFINITY);  // NaN or infinite: the sticky flag (see check())
                 }
             });
         });
@@ -1143,7 +1187,7 @@ struct FixedBody {
             constexpr int I = decltype(i)::value, COL = LDPC_VT(COLS)[P::C0 + I];
             constexpr int P0 = G::COL_PTR[COL], DV = G::COL_PTR[COL + 1] - P0;
             cllr[I] = L.llr_at(COL * 4 * G::Z + L.k4);
-            nan |= is_zero_sign(cllr[I]);
+            nan |= !(fabsf(cllr[I]) < INFINITY);
             sfor<DV>([&](auto jj) {
                 constexpr int J = P0 + decltype(jj)::value;
                 if constexpr (P::col_reg(J) >= 0)
@@ -1188,7 +1232,7 @@ struct FixedBody {
             }
         };
         if constexpr (ALGO == LDPC_ALGO_MINSUM && !SLOW && DC >= 2 && DC <= kDirectDc) {
-            // short row on the fast path (no zero, no NaN: the sticky flag, see below): every
+            // short row on the fast path (no NaN: the sticky flag, see below): every
             // output straight from the other inputs, see direct_row
             float pr[3] = {};
             float als = alv;
@@ -1214,13 +1258,17 @@ struct FixedBody {
             // v_med3 as a canonicalising fmaxf
             float m1 = fabsf(v[0]), m2 = pinf;
             two_smallest<DC>(v, m1, m2, ninf);
-            // Fast path: no zero message in the row (then m1 > 0) and no possible NaN in the
-            // workgroup (the sticky flag, see var()): torch.sign is +-1 on every message, so
+            // Fast path: no possible NaN in the workgroup (the sticky flag, see var()).  On a row
+            // without a zero torch.sign is +-1 on every message, so
             //   c2v_e = (par ^ sign(x_e)) * (alpha * (|x_e| == m1 ? m2 : m1))
-            // bit for bit (a tie at m1 puts m1 in m2 too).  Otherwise MinSumStats (exact
-            // torch.sign(0) = 0 and NaN semantics).
-            // the workgroup's sticky flag (init / var) covers zero and NaN inputs: one branch per
-            // phase (check) instead of one per row, and the hot loop holds the fast code only
+            // bit for bit (a tie at m1 puts m1 in m2 too).  A row with a zero message x_z has
+            // m1 = 0: every other output is +-(alpha * 0) where the reference has sign 0 times
+            // alpha * 0, and output z is the others' parity and minimum as in the reference (its
+            // own sign bit is xored out, |x_z| == m1 selects m2).  The values differ in the sign of
+            // a zero at most, which no later sum, minimum, decision or syndrome can see
+            // (tests/test_minsum_zeros_host.py).  Otherwise MinSumStats (exact NaN semantics).
+            // The workgroup's sticky flag (init / var) covers non-finite inputs: one branch per
+            // phase instead of one per row, and the hot loop holds the fast code only
             if (!SLOW) {
                 // the sign mask and alpha as VGPR operands: an SGPR (or SGPR-held constant) source
                 // halves a VALU op's issue rate (tools/ubench), so the per-edge v_bitop3 below and
@@ -1264,14 +1312,14 @@ struct FixedBody {
 
     template <bool DEC>
     __device__ __forceinline__ void check(const Ctx &C, const Lane &L, int &errs) {
-        if constexpr (ALGO == LDPC_ALGO_MINSUM) {
+        if constexpr (ALGO == LDPC_ALGO_MINSUM && !BAIL) {
             if (__builtin_amdgcn_readfirstlane(*C.flag) != 0)
                 rows<DEC, true>(C, L, errs);
             else
                 rows<DEC, false>(C, L, errs);
             return;
         }
-        rows<DEC, false>(C, L, errs);
+        rows<DEC, false>(C, L, errs);  // BAIL: flood_drive has tested the flag
     }
 
     template <bool DEC, bool SLOW>
@@ -1357,8 +1405,7 @@ struct FixedBody {
     }
 
     template <int TK, bool DEC, bool WRITE>
-    __device__ __forceinline__ void task(const Ctx &C, const Lane &L, const TaskIn &in, int &errs, bool &bad,
-                                         float &mz) {
+    __device__ __forceinline__ void task(const Ctx &C, const Lane &L, const TaskIn &in, int &errs, bool &bad) {
         using K = Task<TK>;
         constexpr int DA = K::DA, DB = K::DB, LO = K::LO, HI = K::HI;
         f32x2 P2;
@@ -1401,24 +1448,15 @@ struct FixedBody {
                 if constexpr (E < DB) {
                     v2c_out<K::PA + E>(acc2[E].x);
                     v2c_out<K::PB + E>(acc2[E].y);
-                    // smallest |v2c| written, register edges included: a zero sets the flag
-                    // (v_minimum3: no canonicalising v_max; a NaN here implies a non-finite APP,
-                    // caught by `bad`)
-                    if constexpr (ALGO == LDPC_ALGO_MINSUM) mz = vmin(vmin(mz, fabsf(acc2[E].x)), fabsf(acc2[E].y));
                 } else {
                     v2c_out<K::PA + E>(accA[E]);
-                    if constexpr (ALGO == LDPC_ALGO_MINSUM) {
-                        // two A-only outputs per v_minimum3
-                        if constexpr ((E - (DB > LO ? DB : LO)) % 2 == 1)
-                            mz = vmin(vmin(mz, fabsf(accA[E - 1])), fabsf(accA[E]));
-                        else if constexpr (E == HI - 1)
-                            mz = vmin(mz, fabsf(accA[E]));
-                    }
                 }
             });
         }
         // a NaN v2c implies a NaN or infinite APP of its column (every summand of a v2c is a
-        // summand of the APP; +-inf is absorbing), so this flag bounds the fast check path
+        // summand of the APP; +-inf is absorbing), so this flag bounds the fast check path.  A zero
+        // v2c needs no flag: the fast forms give the reference's values up to the sign of a zero
+        // (DESIGN.md 3.1 "Exactness of the fast path", tests/test_minsum_zeros_host.py)
         if constexpr (HI == DA) {
             if constexpr (ALGO == LDPC_ALGO_MINSUM) bad |= !(fabsf(PA) < INFINITY);
             if constexpr (DEC) {
@@ -1436,7 +1474,6 @@ struct FixedBody {
     template <bool DEC, bool WRITE>
     __device__ __forceinline__ void var(const Ctx &C, const Lane &L, int &errs) {
         bool bad = false;
-        float mz = INFINITY;
         if constexpr (P::NT > 0) {
             // software pipelining: the next task's reads are issued before the current task's adds
             // when the two hold at most kVarPipe messages together (slots are disjoint between
@@ -1452,21 +1489,19 @@ struct FixedBody {
                 constexpr bool ahead = more && Task<I>::NMSG + Task<(more ? I + 1 : I)>::NMSG <= kVarPipe;
                 if constexpr (I % 2 == 0) {
                     if constexpr (ahead) load_task<I + 1>(C, tb);
-                    task<I, DEC, WRITE>(C, L, ta, errs, bad, mz);
+                    task<I, DEC, WRITE>(C, L, ta, errs, bad);
                     if constexpr (more && !ahead) load_task<(more ? I + 1 : I)>(C, tb);
                 } else {
                     if constexpr (ahead) load_task<I + 1>(C, ta);
-                    task<I, DEC, WRITE>(C, L, tb, errs, bad, mz);
+                    task<I, DEC, WRITE>(C, L, tb, errs, bad);
                     if constexpr (more && !ahead) load_task<(more ? I + 1 : I)>(C, ta);
                 }
             });
             if constexpr (WRITE) addtid_end();
         }
         if constexpr (ALGO == LDPC_ALGO_MINSUM) {
-            bad |= mz == 0.0f;
             if (__any(bad) && L.lane == 0) *C.flag = 1;
         }
-        (void)mz;
     }
 
     __device__ __forceinline__ int parity(const Ctx &C, const Lane &L) const {
@@ -1505,10 +1540,12 @@ __device__ __forceinline__ void fx_by_wave(int wave, F &&f) {
 
 // 4 workgroups per CU without early stop (LDS: 159 slots x 256 B + 8 B each); the early-stop
 // modes also keep Nb + 1 ballot words in LDS, which leaves room for 3, so they may use 168 VGPRs
-template <class G, int ALGO, int ES>
+// BAIL (min-sum, stopping off or per frame, redo != NULL): see FixedBody
+template <class G, int ALGO, int ES, bool BAIL = false>
 __global__ __launch_bounds__(256, ES == LDPC_ES_OFF ? 4 : 3) void flood_fixed_kernel(FloodTables T, const float *__restrict__ llr,
                                                           int64_t B, int max_iter, float alpha, int out_dtype,
-                                                          void *__restrict__ bits, Outs O, EsWs W) {
+                                                          void *__restrict__ bits, Outs O, EsWs W, uint32_t *redo) {
+    static_assert(!BAIL || ES == LDPC_ES_OFF || ES == LDPC_ES_FRAME, "the batch-stop passes share state across workgroups");
     extern __shared__ __attribute__((aligned(16))) char lds[];
 #ifdef LDPC_TIMELINE
     const uint64_t t_in = tl_now();
@@ -1522,8 +1559,9 @@ __global__ __launch_bounds__(256, ES == LDPC_ES_OFF ? 4 : 3) void flood_fixed_ke
     const Lane L = make_lane(Tc, llr, B);
     Ctx C;
     init_ctx(C, Tc, lds, alpha, out_dtype, bits);
+    if constexpr (BAIL) C.redo = redo;
     fx_by_wave<G>(__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), [&](auto wv) {
-        FixedBody<G, ALGO, decltype(wv)::value> body;
+        FixedBody<G, ALGO, decltype(wv)::value, BAIL, reg_edge_cap<ES, BAIL>()> body;
         flood_drive<ES>(body, C, L, B, max_iter, O, W);
 #ifdef LDPC_TIMELINE
         if constexpr (ES == LDPC_ES_OFF) tl_bracket(O.timeline, decltype(wv)::value, t_in);

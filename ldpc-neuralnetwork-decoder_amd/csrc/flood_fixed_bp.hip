@@ -36,7 +36,8 @@ int launch_fixed_bp(int fixed_id, int es, dim3 grid, dim3 block, size_t lds, hip
     void *bi = bits;
     Outs o = O;
     EsWs w = W;
-    void *args[] = {&t, &l, &b, &mi, &a, &od, &bi, &o, &w};
+    uint32_t *rd = nullptr;  // min-sum only
+    void *args[] = {&t, &l, &b, &mi, &a, &od, &bi, &o, &w, &rd};
     LDPC_HIP(hipLaunchKernel(kern, grid, block, args, lds, s));
     return LDPC_OK;
 }

@@ -6,9 +6,14 @@ namespace ldpc {
 
 int launch_fixed_minsum(int fixed_id, int es, dim3 grid, dim3 block, size_t lds, hipStream_t s,
                         const FloodTables &T, const float *llr, int64_t B, int max_iter, float alpha,
-                        int out_dtype, void *bits, const Outs &O, const EsWs &W) {
+                        int out_dtype, void *bits, const Outs &O, const EsWs &W, uint32_t *redo) {
     auto pick = [&](auto code) -> const void * {
         using G = decltype(code);
+        // with a redo list: the instances without the exact check update (they leave the decode
+        // instead, run_flood launches flood_redo_kernel behind them)
+        if (redo && es == LDPC_ES_OFF) return reinterpret_cast<const void *>(flood_fixed_kernel<G, LDPC_ALGO_MINSUM, LDPC_ES_OFF, true>);
+        if (redo && es == LDPC_ES_FRAME) return reinterpret_cast<const void *>(flood_fixed_kernel<G, LDPC_ALGO_MINSUM, LDPC_ES_FRAME, true>);
+        if (redo) return nullptr;
         switch (es) {
             case LDPC_ES_OFF: return reinterpret_cast<const void *>(flood_fixed_kernel<G, LDPC_ALGO_MINSUM, LDPC_ES_OFF>);
             case LDPC_ES_FRAME: return reinterpret_cast<const void *>(flood_fixed_kernel<G, LDPC_ALGO_MINSUM, LDPC_ES_FRAME>);
@@ -30,7 +35,8 @@ int launch_fixed_minsum(int fixed_id, int es, dim3 grid, dim3 block, size_t lds,
     void *bi = bits;
     Outs o = O;
     EsWs w = W;
-    void *args[] = {&t, &l, &b, &mi, &a, &od, &bi, &o, &w};
+    uint32_t *rd = redo;
+    void *args[] = {&t, &l, &b, &mi, &a, &od, &bi, &o, &w, &rd};
     LDPC_HIP(hipLaunchKernel(kern, grid, block, args, lds, s));
     return LDPC_OK;
 }

@@ -15,10 +15,14 @@ int reduce_counter_rows(const uint32_t *partials, int64_t nwg, uint64_t *counter
                         const int32_t *gate, hipStream_t s);
 
 // flood_fixed_ms.hip / flood_fixed_bp.hip: flood_fixed_kernel<code, ALGO, es> for fixed_id 1 (BG2 Z=4)
-// or 2 (BG2 Z=32), es one of LDPC_ES_OFF / LDPC_ES_FRAME / LDPC_ES_BATCH / ES_P1 / ES_P2
+// or 2 (BG2 Z=32), es one of LDPC_ES_OFF / LDPC_ES_FRAME / LDPC_ES_BATCH / ES_P1 / ES_P2.
+// redo (min-sum, LDPC_ES_OFF / LDPC_ES_FRAME only; may be NULL): [0] a count the caller has zeroed,
+// [1 ..] room for one entry per workgroup.  With it the kernel holds the fast check update only: a
+// workgroup that meets a non-finite value appends its index and writes no counter row, and the
+// caller decodes the listed groups again with the table-driven kernel (flood.hip run_flood).
 int launch_fixed_minsum(int fixed_id, int es, dim3 grid, dim3 block, size_t lds, hipStream_t s, const FloodTables &T,
                         const float *llr, int64_t B, int max_iter, float alpha, int out_dtype, void *bits,
-                        const Outs &O, const EsWs &W);
+                        const Outs &O, const EsWs &W, uint32_t *redo);
 int launch_fixed_bp(int fixed_id, int es, dim3 grid, dim3 block, size_t lds, hipStream_t s, const FloodTables &T,
                     const float *llr, int64_t B, int max_iter, float alpha, int out_dtype, void *bits, const Outs &O,
                     const EsWs &W);

@@ -22,9 +22,11 @@ CODES = [("BG2_Z4", os.path.join(ROOT, "codes", "NR_2_0_4.txt"), 4),
 W = 4
 DIRECT_DC = 6  # the default of LDPC_DIRECT_DC in csrc/flood_dev.hpp
 # Register edges (RE_* arrays, LDPC_REG_EDGES in csrc/flood_dev.hpp): at most this many messages
-# per wave stay in VGPRs.  The largest value at which every min-sum and BP instance of both codes
-# keeps its register budget (128 VGPRs without early stop, 168 with, no scratch).
-REG_EDGE_CAP = 8
+# per wave stay in VGPRs.  Above what the search finds for either code (BG2 Z=32: 11 per wave, 44;
+# BG2 Z=4: 15 / 14 / 14 / 15, 58), so every eligible edge is taken; a larger cap finds no more (at
+# Z=4 it only spreads the same 58 less evenly).  The kernel instances that cannot afford them all
+# keep the first LDPC_SLOW_REG_EDGES of a wave's (csrc/flood_dev.hpp FxPlan).
+REG_EDGE_CAP = 16
 # modelled LDS cycles a register edge saves: the check phase's per-edge term of the row costs, and
 # the read and the write of var_task_cost
 CHK_EDGE_LDS = 2.0
