@@ -128,6 +128,11 @@ int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_llr, int64_t
  * Synchronises the stream.  LDPC_EUNSUPPORTED for a decode that keeps no such list. */
 int ldpc_flood_redo_count(const ldpc_graph *g, int algo, int64_t B, int max_iter, int early_stop,
                           const void *d_work, void *stream, int32_t *h_count, int32_t *h_groups);
+/* The sum-product decoders' own float32 functions, element by element (for unit tests):
+ * d_tanh_half[i] = tanh(d_x[i] / 2) and d_two_atanh[i] = 2 atanh(d_x[i]) exactly as the check
+ * update evaluates them.  Either output may be NULL. */
+int ldpc_bp_math_raw(const float *d_x, int64_t n, float *d_tanh_half, float *d_two_atanh,
+                     void *stream);
 
 /* ------------------------------------------------------------------ hybrid min-sum
  * Replaces: CustomMinSumMessageGNNDecoder.forward (models/message_gnn_decoder.py:1167-1251) with

@@ -137,6 +137,16 @@ __global__ __launch_bounds__(512) void batch_emit_kernel(FloodTables T, const ui
 
 __global__ void fill_i32_kernel(int32_t *p, int32_t v) { *p = v; }
 
+// the sum-product decoders' two functions on their own (ldpc_bp_math_raw: unit tests)
+__global__ __launch_bounds__(256) void bp_math_kernel(const float *__restrict__ x, int64_t n,
+                                                      float *__restrict__ th, float *__restrict__ at) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = x[i];
+    if (th) th[i] = tanh_half(v);
+    if (at) at[i] = two_atanh(v);
+}
+
 // Second launch behind a bail-out instance of flood_fixed_kernel (flood_dev.hpp Body::kBail): the
 // groups on its redo list are decoded again from their LLRs by the table-driven update, which is
 // bit-identical and exact for every value, and get their bits, iteration counts and counter rows
@@ -425,6 +435,16 @@ extern "C" int ldpc_flood_redo_count(const ldpc_graph *g, int algo, int64_t B, i
         if ((int64_t)n > (B + g->FG - 1) / g->FG) return fail(LDPC_EINVAL, "d_work holds no redo list of this decode");
         LDPC_HIP(hipMemcpy(h_groups, ws.redo + 1, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
+    return LDPC_OK;
+}
+
+extern "C" int ldpc_bp_math_raw(const float *d_x, int64_t n, float *d_tanh_half, float *d_two_atanh, void *stream) {
+    if (n < 0 || n > 2147483647LL * 256) return fail(LDPC_EINVAL, "bad n");
+    if (n == 0) return LDPC_OK;
+    if (!d_x || (!d_tanh_half && !d_two_atanh)) return fail(LDPC_EINVAL, "x / both outputs are NULL");
+    hipLaunchKernelGGL(bp_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), d_x, n, d_tanh_half, d_two_atanh);
+    LDPC_CHECK_LAUNCH("bp_math_kernel");
     return LDPC_OK;
 }
 

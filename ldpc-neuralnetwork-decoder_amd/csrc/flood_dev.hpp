@@ -325,9 +325,12 @@ struct MinSumFast {
 // versions, 1 ulp; neither is correctly rounded).  Small arguments: the odd minimax polynomials of
 // the Cephes float library (tanh |y| < 0.625, atanh |p| < 0.5; 1.1 and 1.4 ulp in float
 // arithmetic); larger ones: the exp / log forms on the hardware v_exp_f32 / v_log_f32 / v_rcp_f32.
-// Measured against double: <= 1.5e-7 relative with exact exp2/log2/rcp.  Saturation as in the
-// reference: tanh rounds to +-1 for |y| >~ 9, and 2 atanh(+-1) = +-inf.  ~16 + ~18 VALU per edge
-// against ~130 for the ROCm libm calls (and 4x that for double).
+// Measured against double on the device (tests/test_bp_math_gpu.py, every float32 around the branch
+// switches and 4096 per binary exponent): tanh_half <= 1.75e-7 relative (1.63 ulp, the same with
+// exact exp2 / rcp), two_atanh <= 2.01e-7 (2.58 ulp; 1.63e-7 / 1.92 ulp with exact rcp / log2); the
+// tests' bar is 3e-7.  Saturation as in the reference: |tanh| <= 1 always, +-1 for |y| >~ 9, -0 at
+// -0, and 2 atanh(+-1) = +-inf; NaN goes through both.  ~16 + ~18 VALU per edge against ~130 for
+// the ROCm libm calls (and 4x that for double).
 __device__ __forceinline__ float tanh_half(float v) {
     const float y = v * 0.5f;  // exact, = v / 2
     const float a = fabsf(y), z = y * y;
@@ -335,10 +338,12 @@ __device__ __forceinline__ float tanh_half(float v) {
     p = fmaf(p, z, -5.37397155531e-2f);
     p = fmaf(p, z, 1.33314422036e-1f);
     p = fmaf(p, z, -3.33332819422e-1f);
-    const float small = fmaf(p * z, y, y);
+    // both branches on |y|, the sign put back last: fmaf(p * z, y, y) is (+0) + (-0) = +0 at y = -0,
+    // and tanh(-0) is -0 (for y != 0 this is the same bits: rounding to nearest is symmetric)
+    const float small = fmaf(p * z, a, a);
     const float e = __builtin_amdgcn_exp2f(a * 2.88539008177792681f);  // exp(2a)
     const float big = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-    return a < 0.625f ? small : copysignf(big, y);
+    return copysignf(a < 0.625f ? small : big, y);
 }
 __device__ __forceinline__ float two_atanh(float x) {
     const float z = x * x;

@@ -43,6 +43,7 @@ SIGNATURES = {
                                          ctypes.c_int, _P, _P, _P, _P, _P, _I64, _P]),
     "ldpc_flood_redo_count": (ctypes.c_int, [_P, ctypes.c_int, _I64, ctypes.c_int, ctypes.c_int, _P, _P, _P,
                                                  _P]),
+    "ldpc_bp_math_raw": (ctypes.c_int, [_P, _I64, _P, _P, _P]),
     "ldpc_awgn_llr": (ctypes.c_int, [_U64, _U64, _F32, _P, _I64, ctypes.c_int, ctypes.c_int, _P, _P]),
     "ldpc_philox_raw": (ctypes.c_int, [_U64, ctypes.c_uint32, ctypes.c_uint32, _I64, _P, _P]),
     "ldpc_count_errors": (ctypes.c_int, [_P, ctypes.c_int, _P, _I64, ctypes.c_int, _P, _P]),

@@ -46,6 +46,8 @@ def lib():
                                               ctypes.c_int64, P]
         _lib.ldpc_oracle_set_threads.argtypes = [ctypes.c_int]
         _lib.ldpc_oracle_set_threads.restype = ctypes.c_int
+        _lib.ldpc_oracle_set_bp_math.argtypes = [ctypes.c_int]
+        _lib.ldpc_oracle_set_bp_math.restype = ctypes.c_int
         _lib.ldpc_oracle_custom_minsum.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P, P, P,
                                                    ctypes.c_int64, ctypes.c_int, P]
         _lib.ldpc_oracle_custom_minsum.restype = ctypes.c_int
@@ -56,6 +58,13 @@ def set_threads(n):
     """Host threads of flood_decode's frame loop (OpenMP); returns the count in use.  Only the
     timed CPU baseline (bench.py) uses more than 1."""
     return lib().ldpc_oracle_set_threads(int(n))
+
+
+def set_bp_math(mode):
+    """BP's tanh / atanh in flood_decode: 0 (default) = evaluated in double and rounded once, what the
+    golden fixtures pin; 1 = the C library's float32 tanhf / atanhf, a second float32 rounding of the
+    same math.  Returns the mode in use.  Process-wide: a test that sets 1 restores 0."""
+    return lib().ldpc_oracle_set_bp_math(int(mode))
 
 
 def _p(a):
