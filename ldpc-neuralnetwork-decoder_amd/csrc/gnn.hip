@@ -50,18 +50,14 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kMfmaH = 64;
 // other hidden widths run on gnn_mlp_generic_kernel: 4 waves x 4 H floats of LDS (64 KB at 1024)
 constexpr int kMaxGenericH = 1024;
-#ifndef LDPC_MLP2_WPS
-#define LDPC_MLP2_WPS 3
-#endif
-#ifndef LDPC_MLP2_NT
-#define LDPC_MLP2_NT 768
-#endif
-#ifndef LDPC_PROJ_WPS
-#define LDPC_PROJ_WPS 2
-#endif
-#ifndef LDPC_PROJ_NT
-#define LDPC_PROJ_NT 768
-#endif
+// workgroup sizes and waves per SIMD of the H = 64 projected-group kernels (tuned in rounds 3-5)
+constexpr int kMlp2Wps = 3, kMlp2Nt = 768;
+// projection workgroups of 12 waves (one LDS weight image for 12 waves' gathers) when the type table
+// leaves room, else 4 waves at kProjWps per SIMD
+constexpr int kProjWps = 2, kProjNt = 768;
+// 2 waves per SIMD: both sides' GEMM1 share one split of c (226 VGPRs, no spills); 51.6 k vs 49.9 k
+// cw/s for the per-side form at 3 waves per SIMD (168 VGPRs, spilling), profiles/r04
+constexpr int kMlp2sWps = 2, kMlp2sNt = 512;
 // LDPC_GNN_D1=0 keeps the Mv rows of degree-1 var groups (A/B runs)
 bool d1_skip() {
     static bool t = [] {
@@ -495,7 +491,7 @@ struct ProjTiles {
 // the LLRs), and that branch's registers (two members x 8 groups x float4 rows and their types in
 // flight) were what spilled the whole 12-wave kernel (20 VGPRs at the 168-VGPR budget).
 template <int NT, bool HYB = false, bool F16 = true, bool GEN = true>
-__global__ __launch_bounds__(NT, (NT == 256 ? LDPC_PROJ_WPS : 2)) void gnn_group_proj_kernel(GnnLayer P, ProjTiles T) {
+__global__ __launch_bounds__(NT, (NT == 256 ? kProjWps : 2)) void gnn_group_proj_kernel(GnnLayer P, ProjTiles T) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     __shared__ int wmax_bits;
@@ -919,97 +915,62 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2_kernel(GnnLayer P) {
 
 
 // ------------------------------------------------------------------------ MLP over projected groups, fp32 by split MFMAs
-// Default (LDPC_S6_F16, round 5): scaled two-term f16 splits.  The weights are scaled by one power of
+// Scaled two-term f16 splits (round 5).  The weights are scaled by one power of
 // two (largest |w| to at most 2^15), each message's activation column by another (its largest
 // |value|, bounded by max |x| + max |emb[type]| for GEMM1 and by max relu(h) over both sides for
 // GEMM2), so v = v0 + v1 with v0 = f16(v), v1 = f16(v - v0) holds 22 significant bits in the f16
 // normal range, and a product is a1 b0 + a0 b1 + a0 b0 on v_mfma_f32_32x32x16_f16 (the dropped a1 b1
 // is below 2^-22 of the column's largest product); the accumulators start from the scaled additive
-// term and are scaled back exactly after the GEMM.  3 MFMAs per K = 16 instead of 6: 61.4-61.6 k vs
-// 57.0-57.2 k cw/s on cfg4 (profiles/r05/ab_r05f16e); test_split_mlp_is_fp32_accurate holds its bar
-// (error against the float64 oracle within 2x of an fp32 GEMM's).  The bf16x6 form below remains the
-// LDPC_S6_F16=0 build:
-// gnn_mlp2_kernel's math with every fp32 product on v_mfma_f32_32x32x16_bf16: each fp32 operand is
-// split into three bf16 terms, v = v0 + v1 + v2 (v0 = bf16(v), v1 = bf16(v - v0), v2 = bf16(v - v0 -
-// v1): 24 significant bits, every subtraction exact), and a product a b is the six terms
-// a2 b0 + a1 b1 + a0 b2 + a1 b0 + a0 b1 + a0 b0 (the dropped ones are below 2^-24 |a b|), each exact
-// in the fp32 accumulator.  The result is an fp32 GEMM up to summation order -- the same class of
-// difference as between any two fp32 GEMMs -- at 6 x 32 instead of 8 x 64 MFMA cycles per K = 16
-// (2.67x less matrix time).  Weights: three split images per matrix in LDS (bf16, 72-element rows,
-// conflict-free ds_read_b128); activations (c for GEMM1, relu(h) for GEMM2) are split in registers.
+// term and are scaled back exactly after the GEMM.  3 MFMAs per K = 16 instead of the 6 of the
+// three-term bf16 form this kernel had before: 61.4-61.6 k vs 57.0-57.2 k cw/s on cfg4
+// (profiles/r05/ab_r05f16e); test_split_mlp_is_fp32_accurate holds its bar (error against the float64
+// oracle within 2x of an fp32 GEMM's).  The bf16x6 build of this kernel was removed (DESIGN.md 2,
+// "Message GNN (fp32)"); that form lives on in gnn_wide.hip's run-time fallback and the trainer's backward.
+// Weights: two split images per matrix in LDS; activations (c for GEMM1, relu(h) for GEMM2) are split
+// in registers.
 // K order: GEMM1's k-step s, lane half h, element i is unit pi16(16 s + 8 h + i) =
 // 32 (s>>1) + 16 (s&1) + 8 (i>>2) + 4 h + (i&3), which is the unit that lane owns in register
 // 8 (s&1) + i of accumulator tile s>>1: so GEMM2's B operand is GEMM1's accumulator as it stands,
 // and the x values loaded for GEMM1 are the residual the lane adds to its output registers.
-// LDPC_S6_F16 (default): the MLP's fp32 products as scaled two-term f16 splits (3 MFMAs per product)
-// instead of three-term bf16 splits (6); LDPC_S6_PCEARLY: the check side's projected row seeds the
-// accumulators (the f16 kernel's registers have no room for the late add)
-#ifndef LDPC_S6_F16
-#define LDPC_S6_F16 1
-#endif
-#ifndef LDPC_S6_PCEARLY
-#define LDPC_S6_PCEARLY LDPC_S6_F16
-#endif
-#if LDPC_S6_F16
+// The check side's projected row seeds the accumulators (the kernel's registers have no room for a
+// late add).
 typedef _Float16 s6_t;
 typedef f16x8_t s6x8_t;
 constexpr int kS6Split = 2;
-#else
-typedef __bf16 s6_t;
-typedef bf16x8_t s6x8_t;
-constexpr int kS6Split = 3;
-#endif
-// LDPC_S6_PCLDS (default): the row walk copies its unit's 32 projected check rows into LDS at the
-// unit's first tile (lane-private slots), so the unit's other tiles do not re-read them from L2,
-// where the walk's streaming rows have long evicted them (+7.1 % on gnn-z32, profiles/r05/ab_r05pcl);
-// it needs the swizzled unpadded weight images (LDPC_S6_SW) to fit 160 KB
-#ifndef LDPC_S6_PCLDS
-#define LDPC_S6_PCLDS 1
-#endif
-#ifndef LDPC_S6_SW
-#define LDPC_S6_SW LDPC_S6_PCLDS
-#endif
-#if LDPC_S6_SW
+// The row walk copies its unit's 32 projected check rows into LDS at the unit's first tile
+// (lane-private slots), so the unit's other tiles do not re-read them from L2, where the walk's
+// streaming rows have long evicted them (+7.1 % on gnn-z32, profiles/r05/ab_r05pcl); to fit 160 KB the
+// weight images are unpadded and swizzled
 constexpr int kS6Row = 64;                                         // elements per image row
-#else
-constexpr int kS6Row = 72;                                         // elements per image row
-#endif
 constexpr int kS6Img = 64 * kS6Row;                                // elements per split image
-// element (row o, column p) of a split image: padded rows, or 128-B rows whose 16-B chunks are
-// XOR-swizzled by row pair (a fragment read's 16 lanes then cover all 64 banks)
+// element (row o, column p) of a split image: 128-B rows whose 16-B chunks are XOR-swizzled by row
+// pair (a fragment read's 16 lanes then cover all 64 banks)
 __host__ __device__ constexpr int s6_at(int o, int p) {
-#if LDPC_S6_SW
     return o * 64 + ((((p >> 3) ^ ((o >> 1) & 7))) << 3) + (p & 7);
-#else
-    return o * kS6Row + p;
-#endif
 }
 constexpr int kS6OffW2 = 2 * kS6Split * kS6Img;                    // W1L (side, split), then W2
 constexpr int kS6Bytes = 4 * kS6Split * kS6Img * 2;                // 4 matrices x kS6Split images
 constexpr int kS6OffB = kS6Bytes / 4;                              // floats: b2v, b2c, wo
 constexpr int kS6OffEmb = kS6OffB + 3 * 64;                        // floats: emb [T][kPS]
-// then, with degree-1 tiles (GnnLayer tperm), the three split images of W1v_left + W1v_right
-// (f16 splits: then max |emb[t]| per type, T floats)
+// then, with degree-1 tiles (GnnLayer tperm), the split images of W1v_left + W1v_right, then max
+// |emb[t]| per type, T floats
 __host__ __device__ inline int s6_off_d1(int T) { return ((kS6OffEmb + T * kPS + T) * 4 + 15) / 16 * 16; }
 inline size_t mlp2s_lds_bytes(int T, bool d1) { return (size_t)s6_off_d1(T) + (d1 ? kS6Split * kS6Img * 2 : 0); }
-// row walk with LDPC_S6_PCLDS: after the degree-1 image's slot, 8 KB per wave of staged check rows
+// row walk with staged check rows: after the degree-1 image's slot, 8 KB per wave
 __host__ __device__ inline int s6_off_pc(int T) { return s6_off_d1(T) + kS6Split * kS6Img * 2; }
-inline size_t mlp2s_rw_lds_bytes(int T, bool d1, int waves) {
-    return LDPC_S6_PCLDS ? (size_t)s6_off_pc(T) + (size_t)waves * 32 * 64 * 4 : mlp2s_lds_bytes(T, d1);
-}
+inline size_t mlp2s_rw_lds_bytes(int T, int waves) { return (size_t)s6_off_pc(T) + (size_t)waves * 32 * 64 * 4; }
 
 // Degree-1 tiles (tperm set, var side): a degree-1 var group's mean is the message's own c, so
 // W1v [c; g] = (W1v_left + W1v_right) c -- one fp32 sum per weight, rounded once and split like the
 // other weights -- and GEMM1 starts from b1v instead of a projected row, which the projection
 // kernel then does not write for those groups (ProjTiles first = n_ptiles_v1).
-// PCL (row walk only): the units' check rows staged in LDS (LDPC_S6_PCLDS, when the LDS has room)
+// PCL (row walk only): the units' check rows staged in LDS (when the LDS has room)
 template <int NT, int WPS, bool HYB = false, bool RW = false, bool PCL = false>
 __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     s6_t *img = reinterpret_cast<s6_t *>(lds);
     const int tid = threadIdx.x;
     const bool d1img = (P.tperm || RW) && P.ntile_v1 && P.vside;  // the combined image, when degree-1 tiles exist
-#if LDPC_S6_F16
     // one power-of-two scale for every weight image: the largest |w| to at most 2^15
     __shared__ int wmax_bits;
     if (tid == 0) wmax_bits = 0;
@@ -1027,27 +988,18 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
     __syncthreads();
     const int wexp = min(col_exp(__int_as_float(wmax_bits)), 126);
     const float wsc = pow2f(wexp);
-#endif
     for (int i = tid; i < 64 * 64; i += NT) {
         const int o = i >> 6, p = i & 63, u = pi16(p);
         const float w[4] = {P.w1v[o * 128 + u], P.w1c[o * 128 + u], P.w2v[o * 64 + u], P.w2c[o * 64 + u]};
 #pragma unroll
         for (int q = 0; q < 4; ++q)  // q: W1v, W1c, W2v, W2c -> images kS6Split q ..
-#if LDPC_S6_F16
             split2h_store(w[q] * wsc, img + 2 * q * kS6Img + s6_at(o, p), kS6Img);
-#else
-            split_store(w[q], img + 3 * q * kS6Img + s6_at(o, p), kS6Img);
-#endif
     }
     s6_t *img_d1 = reinterpret_cast<s6_t *>(reinterpret_cast<char *>(lds) + s6_off_d1(P.T));
     if (d1img)
         for (int i = tid; i < 64 * 64; i += NT) {
             const int o = i >> 6, p = i & 63, u = pi16(p);
-#if LDPC_S6_F16
             split2h_store((P.w1v[o * 128 + u] + P.w1v[o * 128 + 64 + u]) * wsc, img_d1 + s6_at(o, p), kS6Img);
-#else
-            split_store(P.w1v[o * 128 + u] + P.w1v[o * 128 + 64 + u], img_d1 + s6_at(o, p), kS6Img);
-#endif
         }
     if (tid < 64) {
         lds[kS6OffB + tid] = (P.vside ? P.b2v[tid] : 0.0f) + P.b2c[tid];  // both output biases
@@ -1057,13 +1009,11 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
     // emb rows kPS = 68 floats apart: lanes of different types read different rows (64 apart, every
     // row would sit on the same banks)
     for (int i = tid; i < P.T * 64; i += NT) lds[kS6OffEmb + (i >> 6) * kPS + (i & 63)] = P.emb[i];
-#if LDPC_S6_F16
     for (int t = tid; t < P.T; t += NT) {  // max |emb[t]|: |c| <= max |x| + this bounds a column's scale
         float m = 0.0f;
         for (int u = 0; u < 64; ++u) m = fmaxf(m, fabsf(P.emb[t * 64 + u]));
         lds[kS6OffEmb + P.T * kPS + t] = m;
     }
-#endif
     __syncthreads();
 
     const int lane = tid & 63, j = lane & 31, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform: the walk's indices in SGPRs
@@ -1133,8 +1083,6 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
         f32x16 hs[2][2];
         hs[0][0] = pv[0];
         hs[0][1] = pv[1];
-#if LDPC_S6_PCEARLY
-#if LDPC_S6_PCLDS
         // pcm (uniform): 0 = the check row from global, else from the lane's LDS slots, which the row
         // walk fills at the unit's first tile (float4 q of lane l at pcs[64 q + l]: conflict-free)
         if (PCL && pcm) {
@@ -1148,18 +1096,7 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
         } else {
             load_acc(hs[1], pc);
         }
-#else
-        load_acc(hs[1], pc);
-#endif
-#else
-        // the check side's projected row is added after GEMM1 (its load lands under the MFMAs)
-        f32x16 pcr[2];
-        load_acc(pcr, pc);
-        hs[1][0] = f32x16{};
-        hs[1][1] = f32x16{};
-#endif
         const s6_t *W1v = d1t ? img_d1 : img, *W1c = img + kS6Split * kS6Img;
-#if LDPC_S6_F16
         // the message's c scaled by a power of two (its largest |c| to at most 2^15), the
         // accumulators by that times the weights' scale: products of scaled two-term f16 splits
         float cm = 0.0f;
@@ -1172,10 +1109,8 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
         const float csc = pow2f(cexp), asc = pow2f(cexp + wexp), iasc = pow2f(-cexp - wexp);
         hs[0][0] *= asc;
         hs[0][1] *= asc;
-#if LDPC_S6_PCEARLY
         hs[1][0] *= asc;
         hs[1][1] *= asc;
-#endif
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             float c[8];
@@ -1195,27 +1130,6 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
         hs[0][1] *= iasc;
         hs[1][0] *= iasc;
         hs[1][1] *= iasc;
-#else
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            float c[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) c[i] = x[s][i] + e[pi16(16 * s + 8 * half + i)];
-            bf16x8_t c0, c1, c2;
-            split3(c, c0, c1, c2);
-            if (vs) {
-                hs[0][0] = mfma6(W1v + aof(s), c0, c1, c2, hs[0][0], kS6Img);
-                hs[0][1] = mfma6(W1v + 32 * kS6Row + aof(s), c0, c1, c2, hs[0][1], kS6Img);
-            }
-            hs[1][0] = mfma6(W1c + aof(s), c0, c1, c2, hs[1][0], kS6Img);
-            hs[1][1] = mfma6(W1c + 32 * kS6Row + aof(s), c0, c1, c2, hs[1][1], kS6Img);
-            __builtin_amdgcn_sched_barrier(0);  // one k-step's A fragments live at a time (VGPRs)
-        }
-#endif
-#if !LDPC_S6_PCEARLY
-        hs[1][0] += pcr[0];
-        hs[1][1] += pcr[1];
-#endif
         // GEMM2's accumulators start from the residual and the output biases: register 4 q + i of
         // tile ot is unit 32 ot + 8 q + 4 half + i = x[2 ot + (q >> 1)][4 (q & 1) + i]
         f32x16 y0, y1;
@@ -1237,7 +1151,6 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
                         x[s][4 * q] = v.x; x[s][4 * q + 1] = v.y; x[s][4 * q + 2] = v.z; x[s][4 * q + 3] = v.w;
                     }
         }
-#if LDPC_S6_F16
         // both sides' relu(h) under one column scale (they accumulate into the same y)
         float hm = 0.0f;
 #pragma unroll
@@ -1251,7 +1164,6 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
         const float hsc = pow2f(hexp), ysc = pow2f(hexp + wexp), iysc = pow2f(-hexp - wexp);
         y0 *= ysc;
         y1 *= ysc;
-#endif
 #pragma unroll
         for (int side = 0; side < 2; ++side) {
             if (side == 0 && !vs) continue;
@@ -1262,29 +1174,20 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
                 float hr[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) hr[i] = relu_nan(s < 2 ? h0[8 * (s & 1) + i] : h1[8 * (s & 1) + i]);
-#if LDPC_S6_F16
 #pragma unroll
                 for (int i = 0; i < 8; ++i) hr[i] *= hsc;
                 s6x8_t r0, r1;
                 split2h(hr, r0, r1);
                 y0 = mfma3h(W2 + aof(s), r0, r1, y0, kS6Img);
                 y1 = mfma3h(W2 + 32 * kS6Row + aof(s), r0, r1, y1, kS6Img);
-#else
-                bf16x8_t r0, r1, r2;
-                split3(hr, r0, r1, r2);
-                y0 = mfma6(W2 + aof(s), r0, r1, r2, y0, kS6Img);
-                y1 = mfma6(W2 + 32 * kS6Row + aof(s), r0, r1, r2, y1, kS6Img);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
             if constexpr (RW) {  // the var side is consumed: the next tile's var-side row
                 if (side == 0) load_acc(pv, (d1n ? P.b1v : P.Mv + (bn * P.Gv + vgn) * 64) + 4 * half);
             }
         }
-#if LDPC_S6_F16
         y0 *= iysc;
         y1 *= iysc;
-#endif
         float part = 0.0f;
 #pragma unroll
         for (int ot = 0; ot < 2; ++ot) {
@@ -1373,7 +1276,6 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
             const int typq = P.msg_type[mq], vgq = P.vgroup[mq];
             const int cg = cg0 + (okc ? j : 0);
             if (!P.x_in) load_x(x, b, m, b * P.E + m);  // layer 0: x from the LLR at the tile
-#if LDPC_S6_PCLDS
             if (PCL && i == 0) {  // the unit's first tile: its 32 projected check rows into the lanes' LDS slots
                 const float *pc = P.Mc + (b * P.Gc + cg) * 64 + 4 * half;
                 float4 *pcs = reinterpret_cast<float4 *>(reinterpret_cast<char *>(lds) + s6_off_pc(P.T)) + wave * 512 + lane;
@@ -1386,7 +1288,6 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) pcs[64 * q] = v[q];
             }
-#endif
             tile(b, m, b * P.E + m, okc, P.Mc + (b * P.Gc + cg) * 64 + 4 * half, x, typ, pv, d1,
                  P.x_in + (bq * P.E + mq) * 64 + 4 * half, bq, vgq, d1q, 1);
             if (!inunit) {  // the unit's last tile: its checks' sums
@@ -1735,8 +1636,6 @@ __global__ void gnn_memb_kernel(const float *__restrict__ emb0, int64_t layer_st
     memb[i] = s * inv_c[g];
 }
 
-int64_t layer_floats(int H, int T) { return (int64_t)T * H + 2 * (2LL * H * H + H + (int64_t)H * H + H) + H + 1; }
-
 // H = 32 k other than 64 (gnn_wide.hip) on the MFMA row GEMMs (group plans; inference)
 bool wide_on(const ldpc_gnn_plan *p, int H) { return gnn_wide_supported(H) && !p->weighted && p->n_gtiles > 0; }
 
@@ -1896,20 +1795,10 @@ __global__ void custom_output_kernel(const float *__restrict__ msg_out, const in
     probs[i] = 1.0f / (1.0f + expf(-(s + llr[i])));
 }
 
-int g_num_cus = 0;
+constexpr size_t kLdsMax = 160 * 1024;  // LDS per workgroup on gfx950
 
-constexpr int kMlp2Wps = LDPC_MLP2_WPS, kMlp2Nt = LDPC_MLP2_NT;
-// 2 waves per SIMD: both sides' GEMM1 share one split of c (226 VGPRs, no spills); 51.6 k vs 49.9 k
-// cw/s for the per-side form at 3 waves per SIMD (168 VGPRs, spilling), profiles/r04
-#ifndef LDPC_MLP2S_WPS
-#define LDPC_MLP2S_WPS 2
-#endif
-#ifndef LDPC_MLP2S_NT
-#define LDPC_MLP2S_NT 512
-#endif
-constexpr int kMlp2sWps = LDPC_MLP2S_WPS, kMlp2sNt = LDPC_MLP2S_NT;
 // LDPC_GNN_SPLIT=0: the projected-group MLP on v_mfma_f32_32x32x2_f32 (gnn_mlp2_kernel); default:
-// the same fp32 products as three-term bf16 splits on the bf16 MFMA (gnn_mlp2s_kernel).  Read per
+// the same fp32 products as scaled two-term f16 splits on the f16 MFMA (gnn_mlp2s_kernel).  Read per
 // call (tests compare the two).
 bool split_path() {
     const char *e = std::getenv("LDPC_GNN_SPLIT");
@@ -1951,8 +1840,170 @@ int gnn_streams() {
     return t;
 }
 
+// A GnnLayer's plan part and the call's tensors; the layer loop then sets the layer's weights
+// (set_layer_weights), features and outputs
+GnnLayer plan_layer(const ldpc_gnn_plan *p, int H, int types, const float *d_weights, const int32_t *d_msg_type,
+                    const int32_t *d_msg_var, const float *d_llr, int N, int64_t B, float *Mv, float *Mc) {
+    GnnLayer L{};
+    L.llr = d_llr;
+    L.msg_var = d_msg_var;
+    L.w_in = d_weights;
+    L.b_in = d_weights + H;
+    L.N = N;
+    L.T = types;
+    L.msg_type = d_msg_type;
+    L.vgroup = p->vgroup; L.cgroup = p->cgroup;
+    L.vg_ptr = p->vg_ptr; L.vg_mem = p->vg_mem; L.cg_ptr = p->cg_ptr; L.cg_mem = p->cg_mem;
+    L.inv_v = p->inv_v; L.inv_c = p->inv_c;
+    L.vg_w = p->vg_w; L.cg_w = p->cg_w;
+    L.Gv = p->Gv; L.Gc = p->Gc;
+    L.E = p->E; L.B = B;
+    L.Mv = Mv; L.Mc = Mc;
+    L.vside = 1;
+    return L;
+}
+void set_layer_weights(GnnLayer &L, const GnnLayerWeights<const float *> &w) {
+    L.emb = w.emb;
+    L.w1v = w.w1v; L.b1v = w.b1v; L.w2v = w.w2v; L.b2v = w.b2v;
+    L.w1c = w.w1c; L.b1c = w.b1c; L.w2c = w.w2c; L.b2c = w.b2c;
+    L.wo = w.wo; L.bo = w.bo;
+}
+
+// One kernel instance with its workgroup size, dynamic LDS and workgroups per CU.  The instance is
+// named once, where it is selected: raise_lds and launch both take it from here.
+template <typename... A>
+struct Kernel {
+    void (*fn)(A...);
+    int nt;
+    size_t lds;
+    int per_cu;
+    bool fits() const { return lds <= kLdsMax; }
+    int waves() const { return nt / 64; }
+};
+using ProjKernel = Kernel<GnnLayer, ProjTiles>;
+using MlpKernel = Kernel<GnnLayer>;
+template <typename... A>
+hipError_t raise_lds(const Kernel<A...> &k) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+}
+// grid: one wave per work unit, at most per_cu workgroups per CU
+template <typename... A>
+void launch(const Kernel<A...> &k, int64_t units, int cus, hipStream_t s, A... args) {
+    const unsigned grid = (unsigned)std::min<int64_t>((units + k.waves() - 1) / k.waves(), (int64_t)cus * k.per_cu);
+    hipLaunchKernelGGL(k.fn, dim3(grid), dim3(k.nt), k.lds, s, args...);
+}
+
+// gnn_group_proj_kernel's instance: hyb = the hybrid decoder's check side (4 waves), f16 = the
+// products as f16 splits (else fp32 MFMAs), gen = with the generic typed gather (the row walk's
+// launches go without it).  Workgroups of 12 waves when the type table leaves room, else 4.
+ProjKernel select_proj(int types, bool hyb, bool f16, bool gen) {
+    const bool big = !hyb && proj_lds_bytes(types, kProjNt / 64) <= kLdsMax;
+    ProjKernel k{};
+    k.fn = hyb    ? gnn_group_proj_kernel<256, true>
+           : !f16 ? (big ? gnn_group_proj_kernel<kProjNt, false, false> : gnn_group_proj_kernel<256, false, false>)
+           : !gen ? (big ? gnn_group_proj_kernel<kProjNt, false, true, false> : gnn_group_proj_kernel<256, false, true, false>)
+                  : (big ? gnn_group_proj_kernel<kProjNt> : gnn_group_proj_kernel<256>);
+    k.nt = big ? kProjNt : 256;
+    k.lds = proj_lds_bytes(types, k.waves());
+    k.per_cu = std::max<int>(1, std::min<int>(3, (int)(kLdsMax / k.lds)));
+    return k;
+}
+// The MLP over projected groups: gnn_mlp2s_kernel (split: the tile walk, the row walk rw, the row
+// walk with LDS-staged check rows pc_lds; d1img = with the degree-1 image) or gnn_mlp2_kernel
+MlpKernel select_mlp(int types, bool hyb, bool split, bool rw, bool pc_lds, bool d1img) {
+    MlpKernel k{};
+    if (split) {
+        k.fn = hyb      ? gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, true>
+               : pc_lds ? gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, false, true, true>
+               : rw     ? gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, false, true>
+                        : gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, false>;
+        k.nt = kMlp2sNt;
+        k.lds = pc_lds ? mlp2s_rw_lds_bytes(types, k.waves()) : mlp2s_lds_bytes(types, d1img);
+        k.per_cu = 1;
+    } else {
+        k.fn = hyb ? gnn_mlp2_kernel<kMlp2Nt, kMlp2Wps, true> : gnn_mlp2_kernel<kMlp2Nt, kMlp2Wps>;
+        k.nt = kMlp2Nt;
+        k.lds = mlp2_lds_bytes(types);
+        // workgroups per CU: bounded by LDS and by kMlp2Wps waves per SIMD
+        k.per_cu = std::max<int>(1, std::min<int>(4 * kMlp2Wps / k.waves(), (int)(kLdsMax / k.lds)));
+    }
+    return k;
+}
+// gnn_mlp_tiled_kernel over R message rows (L.wt set)
+int launch_tiled(const GnnLayer &L, int H, int64_t R, int cus, hipStream_t s, const char *what = "gnn_mlp_tiled_kernel") {
+    const int tw = tiled_waves(H);
+    const size_t lds = (size_t)tw * kTiledNM * 4 * H * 4;
+    if (lds > 64 * 1024)
+        LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gnn_mlp_tiled_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t want = (R + (int64_t)tw * kTiledNM - 1) / ((int64_t)tw * kTiledNM);
+    const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)std::max(1, cus * 16 / tw));
+    hipLaunchKernelGGL(gnn_mlp_tiled_kernel, dim3(grid), dim3(64 * tw), lds, s, L, H);
+    LDPC_CHECK_LAUNCH(what);
+    return LDPC_OK;
+}
+// the split MLP (default) unless LDPC_GNN_SPLIT=0, fp32 products are asked for or the type table is too long
+bool split_on(int types, bool fp32_products) {
+    return !fp32_products && split_path() && mlp2s_lds_bytes(types, false) <= kLdsMax;
+}
+
+// Which kernels one fp32 forward runs, decided once per call
+struct Fp32Path {
+    bool mfma;    // H = 64
+    bool wide;    // gnn_wide.hip's layers
+    bool wfused;  // ... with the fused-MLP slice images (H = 96 / 128 on f16 splits)
+    bool proj;    // projected-group path (H = 64, group plans; LDPC_GNN_PROJ=0 selects the per-message
+                  // [c; g] kernels for A/B runs)
+    bool split;   // gnn_mlp2s_kernel
+    bool d1t;     // its tile walk with the degree-1 message tiles first, when the combined image fits
+    bool rw;      // its row walk: check tile groups, per-check sums out of the MLP (carve set S)
+    bool rwd1;    // ... with the plan's degree-1 tile masks
+    bool pc_lds;  // ... with staged check rows: 8 KB per wave beside the images (types up to ~50 at 8 waves)
+    bool gm_d1;   // per-message path: degree-1 var groups get no group-mean row
+    bool too_many_types;  // an LDS image of this path does not hold the type table
+    MlpKernel mfma_k;          // gnn_mlp_mfma_kernel
+    ProjKernel proj_k, proj_rw_k;  // gnn_group_proj_kernel, and without the typed gather
+    MlpKernel mlp_k;           // the MLP over the projected rows
+    bool skip_v1() const { return rw ? rwd1 : d1t; }  // degree-1 var groups have no projected row
+};
+Fp32Path fp32_path(const ldpc_gnn_plan *p, int H, int types, bool train, bool fp32_products, bool have_S, bool have_wimg) {
+    Fp32Path f{};
+    f.mfma = H == kMfmaH;
+    f.wide = wide_on(p, H) && !train;
+    f.wfused = f.wide && !fp32_products && have_wimg && gnn_wide_fused_fits(H, types);
+    f.gm_d1 = H == 64 && gm_tiles() && d1_skip() && !p->weighted;
+    if (!f.mfma) return f;
+    // MLP workgroups of 8 waves (the default of every measured round)
+    f.mfma_k = {gnn_mlp_mfma_kernel<512>, 512, (size_t)(kOffEmb + types * kEmbStride) * 4, 1};
+    f.too_many_types = !f.mfma_k.fits();
+    f.proj = !p->weighted && p->n_ptiles > 0 && proj_path();
+    if (!f.proj || f.too_many_types) return f;
+    const bool d1_fits = mlp2s_lds_bytes(types, true) <= kLdsMax && d1_skip();
+    f.split = split_on(types, fp32_products);
+    f.d1t = f.split && p->n_mtiles_v1 > 0 && d1_fits;
+    f.rw = f.split && have_S && rowwalk_path();
+    f.rwd1 = f.rw && p->rw_d1 && d1_fits;
+    f.pc_lds = f.rw && pclds_path() && mlp2s_rw_lds_bytes(types, kMlp2sNt / 64) <= kLdsMax;
+    f.proj_k = select_proj(types, false, !fp32_products, true);
+    f.proj_rw_k = select_proj(types, false, !fp32_products, false);
+    f.mlp_k = select_mlp(types, false, f.split, f.rw, f.pc_lds, f.skip_v1());
+    f.too_many_types = !f.proj_k.fits() || !f.mlp_k.fits();
+    return f;
+}
+
 }  // namespace
 }  // namespace ldpc
+
+int ldpc::gnn_num_cus(int *cus) {
+    static int n = 0;
+    if (!n) {
+        int dev = 0;
+        LDPC_HIP(hipGetDevice(&dev));
+        LDPC_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+    }
+    *cus = n;
+    return LDPC_OK;
+}
 
 // One non-blocking side stream per device, created once (under a lock) and kept for the process, and a
 // fork/join event pair per device AND calling thread: two host threads decoding on one device record
@@ -1996,27 +2047,16 @@ int ldpc::gnn_build_var_csr(const int32_t *d_msg_var, int64_t E, int N, int32_t 
 
 int ldpc::gnn_output(const float *d_msg_out, const int32_t *d_ints, const float *d_llr, int64_t E, int N, int64_t B,
                      const uint8_t *d_active, float *d_probs, hipStream_t s) {
-    const int64_t n = B * N;
+    int cus = 0;
+    if (int rc = gnn_num_cus(&cus)) return rc;
+    const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)std::max(cus, 1) * 8);
     if (E <= kOutLdsMaxE && B > 0) {
-        if (g_num_cus == 0) {
-            int dev = 0;
-            LDPC_HIP(hipGetDevice(&dev));
-            LDPC_HIP(hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-        }
-        const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)std::max(g_num_cus, 1) * 8);
         hipLaunchKernelGGL(gnn_output_lds_kernel, dim3(grid), dim3(256), (size_t)E * 4, s, d_msg_out, d_ints, d_llr, E, N, B,
                            d_active, d_probs);
         LDPC_CHECK_LAUNCH("gnn_output_lds_kernel");
         return LDPC_OK;
     }
-    if (g_num_cus == 0) {
-        int dev = 0;
-        LDPC_HIP(hipGetDevice(&dev));
-        LDPC_HIP(hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    (void)n;
-    hipLaunchKernelGGL(gnn_output_csr_kernel, dim3((unsigned)std::min<int64_t>(B, (int64_t)std::max(g_num_cus, 1) * 8)), dim3(256),
-                       0, s, d_msg_out, d_ints, d_llr, E, N, B, d_active, d_probs);
+    hipLaunchKernelGGL(gnn_output_csr_kernel, dim3(grid), dim3(256), 0, s, d_msg_out, d_ints, d_llr, E, N, B, d_active, d_probs);
     LDPC_CHECK_LAUNCH("gnn_output_csr_kernel");
     return LDPC_OK;
 }
@@ -2365,7 +2405,7 @@ extern "C" int ldpc_gnn_plan_destroy(ldpc_gnn_plan *p) {
 
 extern "C" int64_t ldpc_gnn_weights_size(int hidden, int types, int layers) {
     if (hidden <= 0 || types <= 0 || layers <= 0) return fail(LDPC_EINVAL, "bad GNN dimensions");
-    return 2LL * hidden + (int64_t)layers * layer_floats(hidden, types);
+    return 2LL * hidden + (int64_t)layers * gnn_layer_floats(hidden, types);
 }
 
 extern "C" int64_t ldpc_gnn_workspace_size(const ldpc_gnn_plan *p, int hidden, int N, int64_t B, int layers,
@@ -2394,270 +2434,155 @@ int ldpc::gnn_fp32_forward(const ldpc_gnn_plan *p, int hidden, int types, int la
     Ws w = carve(p, H, N, B, layers, 0, d_work, train);
     if (!d_work || work_bytes < w.bytes)
         return fail(LDPC_EINVAL, "workspace too small: need " + std::to_string(w.bytes) + " bytes");
-    if (!g_num_cus) {
-        int dev = 0;
-        LDPC_HIP(hipGetDevice(&dev));
-        LDPC_HIP(hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    int cus = 0;
+    if (int rc = gnn_num_cus(&cus)) return rc;
     if (int rc = gnn_build_var_csr(d_msg_var, p->E, N, w.csr, s)) return rc;
-    GnnLayer L{};
-    L.llr = d_llr;
-    L.msg_var = d_msg_var;
-    L.w_in = d_weights;
-    L.b_in = d_weights + H;
-    L.N = N;
-    L.T = types;
-    L.msg_type = d_msg_type;
-    L.vgroup = p->vgroup; L.cgroup = p->cgroup;
-    L.vg_ptr = p->vg_ptr; L.vg_mem = p->vg_mem; L.cg_ptr = p->cg_ptr; L.cg_mem = p->cg_mem;
-    L.inv_v = p->inv_v; L.inv_c = p->inv_c;
-    L.vg_w = p->vg_w; L.cg_w = p->cg_w;
-    L.Gv = p->Gv; L.Gc = p->Gc;
-    L.E = p->E; L.B = B;
-    L.Mv = w.Mv; L.Mc = w.Mc;
-    L.vside = 1;
-    const bool mfma = H == kMfmaH;
-    const bool wide = wide_on(p, H) && !train;
-    if (!mfma && H > kMaxGenericH) return fail(LDPC_EUNSUPPORTED, "hidden_dim must be <= " + std::to_string(kMaxGenericH));
-    const size_t mfma_lds = (size_t)(kOffEmb + types * kEmbStride) * 4;
-    if (mfma && mfma_lds > 160 * 1024) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
-    const int mt = 512;  // MLP workgroups of 8 waves (the default of every measured round)
-    const void *mfma_fn = reinterpret_cast<const void *>(gnn_mlp_mfma_kernel<512>);
-    if (mfma) LDPC_HIP(hipFuncSetAttribute(mfma_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mfma_lds));
-    // projected-group path (H = 64, group plans; LDPC_GNN_PROJ=0 selects the per-message [c; g]
-    // kernels for A/B runs)
-    const bool proj = mfma && !p->weighted && p->n_ptiles > 0 && proj_path();
-    // projection workgroups of 12 waves (one LDS weight image for 12 waves' gathers) when the
-    // type table leaves room, else 4
-    const int proj_nt = LDPC_PROJ_NT != 256 && proj_lds_bytes(types, LDPC_PROJ_NT / 64) <= 160 * 1024 ? LDPC_PROJ_NT : 256;
-    const bool split = !fp32_products && split_path() && mlp2s_lds_bytes(types, false) <= 160 * 1024;
-    // degree-1 message tiles first (gnn_mlp2s_kernel) when the combined image fits
-    const bool d1t = split && p->n_mtiles_v1 > 0 && mlp2s_lds_bytes(types, true) <= 160 * 1024 && d1_skip();
-    // row walk (gnn_mlp2s_kernel RW): check tile groups, per-check sums out of the MLP (w.S set by carve)
-    const bool rw = split && w.S && rowwalk_path();
-    const bool rwd1 = rw && p->rw_d1 && mlp2s_lds_bytes(types, true) <= 160 * 1024 && d1_skip();
-    // the staged check rows need 8 KB per wave beside the images (types up to ~50 at 8 waves)
-    const bool pc_lds = rw && LDPC_S6_PCLDS && pclds_path() && mlp2s_rw_lds_bytes(types, true, kMlp2sNt / 64) <= 160 * 1024;
-    const size_t proj_lds = proj_lds_bytes(types, proj_nt / 64),
-                 mlp2_lds = split ? (pc_lds ? mlp2s_rw_lds_bytes(types, rwd1, kMlp2sNt / 64) : mlp2s_lds_bytes(types, rw ? rwd1 : d1t))
-                                  : mlp2_lds_bytes(types);
-    const void *proj_fn = fp32_products
-                              ? (proj_nt != 256 ? reinterpret_cast<const void *>(gnn_group_proj_kernel<LDPC_PROJ_NT, false, false>)
-                                                : reinterpret_cast<const void *>(gnn_group_proj_kernel<256, false, false>))
-                              : (proj_nt != 256 ? reinterpret_cast<const void *>(gnn_group_proj_kernel<LDPC_PROJ_NT>)
-                                                : reinterpret_cast<const void *>(gnn_group_proj_kernel<256>));
-    // the row walk's projection without the generic typed gather (see gnn_group_proj_kernel)
-    const void *proj_fn_rw = proj_nt != 256 ? reinterpret_cast<const void *>(gnn_group_proj_kernel<LDPC_PROJ_NT, false, true, false>)
-                                            : reinterpret_cast<const void *>(gnn_group_proj_kernel<256, false, true, false>);
-    int mlp2_per_cu = 1, proj_per_cu = 1;
-    if (proj) {
-        if (mlp2_lds > 160 * 1024 || proj_lds > 160 * 1024)
-            return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
-        proj_per_cu = std::max<int>(1, std::min<int>(3, (int)((160 * 1024) / proj_lds)));
-        // workgroups per CU: bounded by LDS and by kMlp2Wps waves per SIMD
-        mlp2_per_cu = std::max<int>(1, std::min<int>(4 * kMlp2Wps / (kMlp2Nt / 64), (int)((160 * 1024) / mlp2_lds)));
-        LDPC_HIP(hipFuncSetAttribute(proj_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)proj_lds));
-        LDPC_HIP(hipFuncSetAttribute(proj_fn_rw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)proj_lds));
-        LDPC_HIP(hipFuncSetAttribute(split ? (rw ? (pc_lds ? reinterpret_cast<const void *>(gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, false, true, true>)
-                                                           : reinterpret_cast<const void *>(gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, false, true>))
-                                                 : reinterpret_cast<const void *>(gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, false>))
-                                           : reinterpret_cast<const void *>(gnn_mlp2_kernel<kMlp2Nt, kMlp2Wps>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp2_lds));
+    if (H != kMfmaH && H > kMaxGenericH) return fail(LDPC_EUNSUPPORTED, "hidden_dim must be <= " + std::to_string(kMaxGenericH));
+    const Fp32Path f = fp32_path(p, H, types, train, fp32_products, w.S != nullptr, w.wimg != nullptr);
+    if (f.too_many_types) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
+    if (f.mfma) LDPC_HIP(raise_lds(f.mfma_k));
+    if (f.proj) {
+        LDPC_HIP(raise_lds(f.proj_k));
+        LDPC_HIP(raise_lds(f.proj_rw_k));
+        LDPC_HIP(raise_lds(f.mlp_k));
     }
-    if (proj && rw) {  // every layer's mean type embedding per check group, once per call
+    // per-call preparation, on the caller's stream before the frame halves fork
+    const float *emb0 = gnn_layer_weights(d_weights, H, types, 0).emb;
+    if (f.proj && f.rw) {  // every layer's mean type embedding per check group and per var group
         const int64_t n = (int64_t)layers * p->Gc * 64;
-        hipLaunchKernelGGL(gnn_memb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_weights + 2 * H,
-                           layer_floats(H, types), d_msg_type, p->cg_ptr, p->cg_mem, p->inv_c, p->Gc, layers, w.memb);
+        hipLaunchKernelGGL(gnn_memb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, emb0,
+                           gnn_layer_floats(H, types), d_msg_type, p->cg_ptr, p->cg_mem, p->inv_c, p->Gc, layers, w.memb);
         LDPC_CHECK_LAUNCH("gnn_memb_kernel");
         const int64_t nv = (int64_t)layers * p->Gv * 64;
-        hipLaunchKernelGGL(gnn_memb_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, d_weights + 2 * H,
-                           layer_floats(H, types), d_msg_type, p->vg_ptr, p->vg_mem, p->inv_v, p->Gv, layers, w.memb_v);
+        hipLaunchKernelGGL(gnn_memb_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, emb0,
+                           gnn_layer_floats(H, types), d_msg_type, p->vg_ptr, p->vg_mem, p->inv_v, p->Gv, layers, w.memb_v);
         LDPC_CHECK_LAUNCH("gnn_memb_kernel");
     }
-    // wide H = 96 / 128 on f16 splits: every layer's fused-MLP slice images, once per call
-    const bool wfused = wide && !fp32_products && w.wimg && gnn_wide_fused_fits(H, types);
-    if (wfused)
-        if (int rc = gnn_wide_prep(H, layers, d_weights, layer_floats(H, types), types, w.wimg, w.wexp, s)) return rc;
-    if (wide && w.wmemb)
-        if (int rc = gnn_wide_memb(p, H, layers, d_weights + 2 * H, layer_floats(H, types), d_msg_type, w.wmemb, s)) return rc;
-    // frames [b0, b0 + nb) through every layer on stream st (pointers offset to the range)
-    const GnnLayer L0 = L;
-    auto run_range = [&](int64_t b0, int64_t nb, hipStream_t st) -> int {
-    GnnLayer L = L0;
-    L.B = nb;
-    L.llr = d_llr + b0 * N;
-    L.Mv = w.Mv + b0 * p->Gv * H;
-    L.Mc = w.Mc + b0 * p->Gc * H;
-    const int64_t xoff = b0 * p->E * H;
-    const float *x_in = nullptr;
-    for (int l = 0; l < layers; ++l) {
-        const float *lw = d_weights + 2 * H + (int64_t)l * layer_floats(H, types);
-        L.emb = lw;
-        L.w1v = L.emb + (int64_t)types * H;
-        L.b1v = L.w1v + 2LL * H * H;
-        L.w2v = L.b1v + H;
-        L.b2v = L.w2v + (int64_t)H * H;
-        L.w1c = L.b2v + H;
-        L.b1c = L.w1c + 2LL * H * H;
-        L.w2c = L.b1c + H;
-        L.b2c = L.w2c + (int64_t)H * H;
-        L.wo = L.b2c + H;
-        L.bo = L.wo + H;
-        L.x_in = x_in;
-        L.residual = l > 0;
-        L.last = l == layers - 1;
-        L.x_out = d_saved ? d_saved + (int64_t)l * B * p->E * H + xoff
-                          : L.last ? nullptr : ((l % 2 == 0) ? w.xa : w.xb) + xoff;
-        L.msg_out = w.msg_out + b0 * p->E;
-        if (wide) {
-            GnnWideLayer W{};
-            W.plan = p;
-            W.H = H; W.T = types; W.N = N; W.B = nb; W.E = p->E;
-            W.x_in = x_in;
-            W.llr = L.llr; W.msg_type = d_msg_type; W.msg_var = d_msg_var; W.w_in = L.w_in; W.b_in = L.b_in;
-            W.emb = L.emb; W.w1v = L.w1v; W.b1v = L.b1v; W.w2v = L.w2v; W.b2v = L.b2v;
-            W.w1c = L.w1c; W.b1c = L.b1c; W.w2c = L.w2c; W.b2c = L.b2c; W.wo = L.wo; W.bo = L.bo;
-            W.Mv = L.Mv; W.Mc = L.Mc;
-            W.Pv = w.Pv + b0 * p->Gv * H; W.Pc = w.Pc + b0 * p->Gc * H;
-            W.hbuf = w.hbuf + b0 * p->E * 2 * H;
-            W.y = L.x_out ? L.x_out : ((l % 2 == 0) ? w.xa : w.xb) + xoff;  // the last layer: a free buffer
-            W.residual = l > 0;
-            W.msg_out = L.last ? L.msg_out : nullptr;
-            W.f16 = !fp32_products;
-            const int64_t roff = b0 * p->E;
-            W.xmax_in = l > 0 ? w.xmax[(l - 1) & 1] + roff : nullptr;
-            W.xmax_out = w.xmax[l & 1] + roff;
-            W.hmax = w.hmax + roff;
-            W.gmax_v = w.gmax_v + b0 * p->Gv;
-            W.gmax_c = w.gmax_c + b0 * p->Gc;
-            W.wimg = wfused ? w.wimg + (int64_t)l * (gnn_wide_fused_bytes(H, 1)) : nullptr;
-            W.wexp = wfused ? w.wexp + 2 * l : nullptr;
-            W.memb = w.wmemb ? w.wmemb + (int64_t)l * (p->Gv + p->Gc) * H : nullptr;
-            if (int rc = gnn_wide_layer(W, st)) return rc;
-            x_in = W.y;
-            continue;
-        }
-        const int64_t waves = nb * (int64_t)(p->Gv + p->Gc);
-        L.d1 = H == 64 && gm_tiles() && d1_skip() && !p->weighted;
-        if (proj) {
-            L.d1 = 0;
-            if (rw) {
-                L.rw_meta = p->rw_meta;
-                L.rw_n = p->n_rw;
-                L.ntile_v1 = rwd1;
-                L.S_in = l > 0 ? w.S + b0 * p->Gc * H : nullptr;
-                L.S_out = l + 1 < layers ? w.S + b0 * p->Gc * H : nullptr;
-                L.memb = w.memb + (int64_t)l * p->Gc * H;
-                L.memb_v = w.memb_v + (int64_t)l * p->Gv * H;
-            } else if (d1t) {
-                L.tperm = p->mt_perm;
-                L.ntile_pf = p->n_mtiles;
-                L.ntile_v1 = p->n_mtiles_v1;
-            }
-            // training with saved projections (d_proj): this layer's projected rows and group means go
-            // to d_proj for the backward, every var group's included (the backward's GEMM1 reads them)
-            bool skip_v1 = rw ? rwd1 : d1t;
-            if (d_proj) {
-                const int64_t G = p->Gv + p->Gc;
-                float *base = d_proj + (int64_t)l * B * G * 2 * H;
-                L.Mv = base + b0 * p->Gv * H;
-                L.Mc = base + B * p->Gv * H + b0 * p->Gc * H;
-                L.gsave_v = base + B * G * H + b0 * p->Gv * H;
-                L.gsave_c = base + B * G * H + B * p->Gv * H + b0 * p->Gc * H;
-                skip_v1 = false;
-            }
-            const ProjTiles T{p->pt_meta, p->pt_grp, p->pt_deg, p->pt_mem, p->n_ptiles, skip_v1 ? p->n_ptiles_v1 : 0};
-            const int64_t ptiles = nb * (int64_t)p->n_ptiles;
-            const int pw = proj_nt / 64;
-            const unsigned pgrid = (unsigned)std::min<int64_t>((ptiles + pw - 1) / pw, (int64_t)g_num_cus * proj_per_cu);
-            // the row walk's tiles never take the typed gather: without x_in they read the LLRs, with it
-            // the check side reads the sums S_in and the var side the mean embeddings memb_v (set above)
-            const bool gen = !(rw && L.memb_v && (!L.x_in || L.S_in));
-            if (!fp32_products && !gen && proj_nt != 256)
-                hipLaunchKernelGGL((gnn_group_proj_kernel<LDPC_PROJ_NT, false, true, false>), dim3(pgrid), dim3(LDPC_PROJ_NT), proj_lds, st, L, T);
-            else if (!fp32_products && !gen)
-                hipLaunchKernelGGL((gnn_group_proj_kernel<256, false, true, false>), dim3(pgrid), dim3(256), proj_lds, st, L, T);
-            else if (fp32_products && proj_nt != 256)
-                hipLaunchKernelGGL((gnn_group_proj_kernel<LDPC_PROJ_NT, false, false>), dim3(pgrid), dim3(LDPC_PROJ_NT), proj_lds, st, L, T);
-            else if (fp32_products)
-                hipLaunchKernelGGL((gnn_group_proj_kernel<256, false, false>), dim3(pgrid), dim3(256), proj_lds, st, L, T);
-            else if (proj_nt != 256)
-                hipLaunchKernelGGL(gnn_group_proj_kernel<LDPC_PROJ_NT>, dim3(pgrid), dim3(LDPC_PROJ_NT), proj_lds, st, L, T);
-            else
-                hipLaunchKernelGGL(gnn_group_proj_kernel<256>, dim3(pgrid), dim3(256), proj_lds, st, L, T);
-            LDPC_CHECK_LAUNCH("gnn_group_proj_kernel");
-            const int64_t tiles = d1t ? nb * p->n_mtiles : (nb * p->E + 31) / 32;
-            constexpr int wpb = kMlp2Nt / 64;
-            const unsigned grid = (unsigned)std::min<int64_t>((tiles + wpb - 1) / wpb, (int64_t)g_num_cus * mlp2_per_cu);
-            if (rw) {
-                const dim3 rgrid((unsigned)std::min<int64_t>((nb * p->n_rw + kMlp2sNt / 64 - 1) / (kMlp2sNt / 64), (int64_t)g_num_cus));
-                if (pc_lds)
-                    hipLaunchKernelGGL((gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, false, true, true>), rgrid, dim3(kMlp2sNt), mlp2_lds, st, L);
-                else
-                    hipLaunchKernelGGL((gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, false, true>), rgrid, dim3(kMlp2sNt), mlp2_lds, st, L);
-            }
-            else if (split)
-                hipLaunchKernelGGL((gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, false>),
-                                   dim3((unsigned)std::min<int64_t>((tiles + kMlp2sNt / 64 - 1) / (kMlp2sNt / 64), (int64_t)g_num_cus)),
-                                   dim3(kMlp2sNt), mlp2_lds, st, L);
-            else
-                hipLaunchKernelGGL((gnn_mlp2_kernel<kMlp2Nt, kMlp2Wps>), dim3(grid), dim3(kMlp2Nt), mlp2_lds, st, L);
-            LDPC_CHECK_LAUNCH("gnn_mlp2_kernel");
-            x_in = L.x_out;
-            continue;
-        }
-        if (p->weighted)  // general adjacency: weighted rows, one wave per (frame, message row)
-            hipLaunchKernelGGL(gnn_group_mean_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, L, H);
-        else if (H == 64 && gm_tiles()) {
-            const GtTiles G{p->gt_meta, p->gt_grp, p->gt_mem, p->n_gtiles, L.d1 ? p->n_gtiles_v1 : 0};
-            const int64_t twaves = nb * (int64_t)(G.n_tiles - G.first);
-            hipLaunchKernelGGL(gnn_group_mean_tile_kernel, dim3((unsigned)((twaves + 3) / 4)), dim3(256), 0, st, L, G);
-        } else if (H == 64)
-            hipLaunchKernelGGL(gnn_group_mean_h64_kernel, dim3((unsigned)((waves + 15) / 16)), dim3(256), 0, st, L);
-        else
-            hipLaunchKernelGGL(gnn_group_mean_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, L, H);
-        LDPC_CHECK_LAUNCH("gnn_group_mean_kernel");
-        if (mfma) {
-            const int64_t tiles = (nb * p->E + 31) / 32;
-            const int64_t want = (tiles + mt / 64 - 1) / (mt / 64);
-            const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)g_num_cus);
-            hipLaunchKernelGGL(gnn_mlp_mfma_kernel<512>, dim3(grid), dim3(512), mfma_lds, st, L);
-            LDPC_CHECK_LAUNCH("gnn_mlp_mfma_kernel");
-        } else {
-            if (w.wt) {  // tiled: kTiledNM messages per wave over the layer's transposed weights
-                GnnLayer T = L;
-                T.wt = w.wt + 6LL * H * H * l;
-                const int tw = tiled_waves(H);
-                const int64_t want = (nb * p->E + (int64_t)tw * kTiledNM - 1) / ((int64_t)tw * kTiledNM);
-                const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)std::max(1, g_num_cus * 16 / tw));
-                const size_t tl = (size_t)tw * kTiledNM * 4 * H * 4;
-                if (tl > 64 * 1024)
-                    LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gnn_mlp_tiled_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)tl));
-                hipLaunchKernelGGL(gnn_mlp_tiled_kernel, dim3(grid), dim3(64 * tw), (size_t)tw * kTiledNM * 4 * H * 4, st,
-                                   T, H);
-                LDPC_CHECK_LAUNCH("gnn_mlp_tiled_kernel");
-            } else {
-                const int64_t want = (nb * p->E + 3) / 4;
-                const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)g_num_cus * 8);
-                hipLaunchKernelGGL(gnn_mlp_generic_kernel, dim3(grid), dim3(256), (size_t)16 * H * 4, st, L, H);
-                LDPC_CHECK_LAUNCH("gnn_mlp_generic_kernel");
-            }
-        }
-        x_in = L.x_out;
-    }
-    return LDPC_OK;
-    };
-    if (w.wt) {  // the tiled kernel's transposed weights of every layer, on the caller's stream
+    // wide H = 96 / 128 on f16 splits: every layer's fused-MLP slice images
+    if (f.wfused)
+        if (int rc = gnn_wide_prep(H, layers, d_weights, types, w.wimg, w.wexp, s)) return rc;
+    if (f.wide && w.wmemb)
+        if (int rc = gnn_wide_memb(p, H, types, layers, d_weights, d_msg_type, w.wmemb, s)) return rc;
+    if (w.wt) {  // the tiled kernel's transposed weights of every layer
         for (int l = 0; l < layers; ++l) {
-            const float *lw = d_weights + 2 * H + (int64_t)l * layer_floats(H, types);
-            const float *w1v = lw + (int64_t)types * H, *w2v = w1v + 2LL * H * H + H;
-            const float *w1c = w2v + (int64_t)H * H + H, *w2c = w1c + 2LL * H * H + H;
-            hipLaunchKernelGGL(gnn_wt_kernel, dim3((unsigned)((6LL * H * H + 255) / 256)), dim3(256), 0, s, w1v, w2v, w1c,
-                               w2c, H, w.wt + 6LL * H * H * l);
+            const auto lw = gnn_layer_weights(d_weights, H, types, l);
+            hipLaunchKernelGGL(gnn_wt_kernel, dim3((unsigned)((6LL * H * H + 255) / 256)), dim3(256), 0, s, lw.w1v, lw.w2v,
+                               lw.w1c, lw.w2c, H, w.wt + 6LL * H * H * l);
             LDPC_CHECK_LAUNCH("gnn_wt_kernel");
         }
     }
+    const GnnLayer L0 = plan_layer(p, H, types, d_weights, d_msg_type, d_msg_var, d_llr, N, B, w.Mv, w.Mc);
+    // frames [b0, b0 + nb) through every layer on stream st (pointers offset to the range)
+    auto run_range = [&](int64_t b0, int64_t nb, hipStream_t st) -> int {
+        GnnLayer L = L0;
+        L.B = nb;
+        L.llr = d_llr + b0 * N;
+        L.Mv = w.Mv + b0 * p->Gv * H;
+        L.Mc = w.Mc + b0 * p->Gc * H;
+        L.msg_out = w.msg_out + b0 * p->E;
+        const int64_t xoff = b0 * p->E * H;
+        for (int l = 0; l < layers; ++l) {
+            const auto lw = gnn_layer_weights(d_weights, H, types, l);
+            set_layer_weights(L, lw);
+            L.residual = l > 0;
+            L.last = l == layers - 1;
+            float *x_next = ((l % 2 == 0) ? w.xa : w.xb) + xoff;
+            L.x_out = d_saved ? d_saved + (int64_t)l * B * p->E * H + xoff : L.last ? nullptr : x_next;
+            if (f.wide) {
+                GnnWideLayer W{};
+                W.plan = p;
+                W.H = H; W.T = types; W.N = N; W.B = nb; W.E = p->E;
+                W.x_in = L.x_in;
+                W.llr = L.llr; W.msg_type = d_msg_type; W.msg_var = d_msg_var; W.w_in = L.w_in; W.b_in = L.b_in;
+                W.w = lw;
+                W.Mv = L.Mv; W.Mc = L.Mc;
+                W.Pv = w.Pv + b0 * p->Gv * H; W.Pc = w.Pc + b0 * p->Gc * H;
+                W.hbuf = w.hbuf + b0 * p->E * 2 * H;
+                W.y = L.x_out ? L.x_out : x_next;  // the last layer: a free buffer
+                W.residual = l > 0;
+                W.msg_out = L.last ? L.msg_out : nullptr;
+                W.f16 = !fp32_products;
+                const int64_t roff = b0 * p->E;
+                W.xmax_in = l > 0 ? w.xmax[(l - 1) & 1] + roff : nullptr;
+                W.xmax_out = w.xmax[l & 1] + roff;
+                W.hmax = w.hmax + roff;
+                W.gmax_v = w.gmax_v + b0 * p->Gv;
+                W.gmax_c = w.gmax_c + b0 * p->Gc;
+                W.wimg = f.wfused ? w.wimg + (int64_t)l * (gnn_wide_fused_bytes(H, 1)) : nullptr;
+                W.wexp = f.wfused ? w.wexp + 2 * l : nullptr;
+                W.memb = w.wmemb ? w.wmemb + (int64_t)l * (p->Gv + p->Gc) * H : nullptr;
+                if (int rc = gnn_wide_layer(W, st)) return rc;
+                L.x_in = W.y;
+                continue;
+            }
+            if (f.proj) {
+                if (f.rw) {
+                    L.rw_meta = p->rw_meta;
+                    L.rw_n = p->n_rw;
+                    L.ntile_v1 = f.rwd1;
+                    L.S_in = l > 0 ? w.S + b0 * p->Gc * H : nullptr;
+                    L.S_out = l + 1 < layers ? w.S + b0 * p->Gc * H : nullptr;
+                    L.memb = w.memb + (int64_t)l * p->Gc * H;
+                    L.memb_v = w.memb_v + (int64_t)l * p->Gv * H;
+                } else if (f.d1t) {
+                    L.tperm = p->mt_perm;
+                    L.ntile_pf = p->n_mtiles;
+                    L.ntile_v1 = p->n_mtiles_v1;
+                }
+                // training with saved projections (d_proj): this layer's projected rows and group means go
+                // to d_proj for the backward, every var group's included (the backward's GEMM1 reads them)
+                bool skip_v1 = f.skip_v1();
+                if (d_proj) {
+                    const int64_t G = p->Gv + p->Gc;
+                    float *base = d_proj + (int64_t)l * B * G * 2 * H;
+                    L.Mv = base + b0 * p->Gv * H;
+                    L.Mc = base + B * p->Gv * H + b0 * p->Gc * H;
+                    L.gsave_v = base + B * G * H + b0 * p->Gv * H;
+                    L.gsave_c = base + B * G * H + B * p->Gv * H + b0 * p->Gc * H;
+                    skip_v1 = false;
+                }
+                const ProjTiles T{p->pt_meta, p->pt_grp, p->pt_deg, p->pt_mem, p->n_ptiles, skip_v1 ? p->n_ptiles_v1 : 0};
+                // the row walk's tiles never take the typed gather: without x_in they read the LLRs, with it
+                // the check side reads the sums S_in and the var side the mean embeddings memb_v (set above)
+                const bool gen = !(f.rw && L.memb_v && (!L.x_in || L.S_in));
+                launch(gen ? f.proj_k : f.proj_rw_k, nb * (int64_t)p->n_ptiles, cus, st, L, T);
+                LDPC_CHECK_LAUNCH("gnn_group_proj_kernel");
+                // one wave per check tile group (row walk) or per 32-message tile
+                const int64_t units = f.rw ? nb * p->n_rw : f.d1t ? nb * p->n_mtiles : (nb * p->E + 31) / 32;
+                launch(f.mlp_k, units, cus, st, L);
+                LDPC_CHECK_LAUNCH("gnn_mlp2_kernel");
+                L.x_in = L.x_out;
+                continue;
+            }
+            L.d1 = f.gm_d1;
+            const int64_t waves = nb * (int64_t)(p->Gv + p->Gc);
+            if (p->weighted || H != 64) {  // weighted: general adjacency, one wave per (frame, message row)
+                hipLaunchKernelGGL(gnn_group_mean_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, L, H);
+            } else if (gm_tiles()) {
+                const GtTiles G{p->gt_meta, p->gt_grp, p->gt_mem, p->n_gtiles, L.d1 ? p->n_gtiles_v1 : 0};
+                const int64_t twaves = nb * (int64_t)(G.n_tiles - G.first);
+                hipLaunchKernelGGL(gnn_group_mean_tile_kernel, dim3((unsigned)((twaves + 3) / 4)), dim3(256), 0, st, L, G);
+            } else {
+                hipLaunchKernelGGL(gnn_group_mean_h64_kernel, dim3((unsigned)((waves + 15) / 16)), dim3(256), 0, st, L);
+            }
+            LDPC_CHECK_LAUNCH("gnn_group_mean_kernel");
+            if (f.mfma) {
+                launch(f.mfma_k, (nb * p->E + 31) / 32, cus, st, L);
+                LDPC_CHECK_LAUNCH("gnn_mlp_mfma_kernel");
+            } else if (w.wt) {  // tiled: kTiledNM messages per wave over the layer's transposed weights
+                GnnLayer T = L;
+                T.wt = w.wt + 6LL * H * H * l;
+                if (int rc = launch_tiled(T, H, nb * p->E, cus, st)) return rc;
+            } else {
+                const int64_t want = (nb * p->E + 3) / 4;
+                const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)cus * 8);
+                hipLaunchKernelGGL(gnn_mlp_generic_kernel, dim3(grid), dim3(256), (size_t)16 * H * 4, st, L, H);
+                LDPC_CHECK_LAUNCH("gnn_mlp_generic_kernel");
+            }
+            L.x_in = L.x_out;
+        }
+        return LDPC_OK;
+    };
     // Two frame halves on two streams (fork / join through events on the caller's stream): every
     // frame's layers stay in order on its stream, and the halves share no data.
     if (gnn_streams() == 2 && B >= 2 * 64) {
@@ -2674,8 +2599,7 @@ int ldpc::gnn_fp32_forward(const ldpc_gnn_plan *p, int hidden, int types, int la
     } else if (int rc = run_range(0, B, s)) {
         return rc;
     }
-    if (int rc = gnn_output(w.msg_out, w.csr, d_llr, p->E, N, B, nullptr, d_probs, s)) return rc;
-    return LDPC_OK;
+    return gnn_output(w.msg_out, w.csr, d_llr, p->E, N, B, nullptr, d_probs, s);
 }
 
 int ldpc::gnn_project_groups(const ldpc_gnn_plan *p, int types, const float *d_weights, int layer, const float *d_x,
@@ -2683,52 +2607,17 @@ int ldpc::gnn_project_groups(const ldpc_gnn_plan *p, int types, const float *d_w
                              int64_t B, float *d_pv, float *d_pc, float *d_gv, float *d_gc, hipStream_t s) {
     constexpr int H = kMfmaH;
     if (p->weighted || p->n_ptiles <= 0) return fail(LDPC_EUNSUPPORTED, "group projection needs a group plan");
-    if (!g_num_cus) {
-        int dev = 0;
-        LDPC_HIP(hipGetDevice(&dev));
-        LDPC_HIP(hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    GnnLayer L{};
+    int cus = 0;
+    if (int rc = gnn_num_cus(&cus)) return rc;
+    GnnLayer L = plan_layer(p, H, types, d_weights, d_msg_type, d_msg_var, d_llr, N, B, d_pv, d_pc);
     L.x_in = d_x;
-    L.llr = d_llr;
-    L.msg_var = d_msg_var;
-    L.w_in = d_weights;
-    L.b_in = d_weights + H;
-    L.N = N;
-    L.T = types;
-    L.msg_type = d_msg_type;
-    L.vgroup = p->vgroup; L.cgroup = p->cgroup;
-    L.vg_ptr = p->vg_ptr; L.vg_mem = p->vg_mem; L.cg_ptr = p->cg_ptr; L.cg_mem = p->cg_mem;
-    L.inv_v = p->inv_v; L.inv_c = p->inv_c;
-    L.Gv = p->Gv; L.Gc = p->Gc;
-    L.E = p->E; L.B = B;
-    L.Mv = d_pv; L.Mc = d_pc;
     L.gsave_v = d_gv; L.gsave_c = d_gc;
-    L.vside = 1;
-    const float *lw = d_weights + 2 * H + (int64_t)layer * layer_floats(H, types);
-    L.emb = lw;
-    L.w1v = L.emb + (int64_t)types * H;
-    L.b1v = L.w1v + 2LL * H * H;
-    L.w2v = L.b1v + H;
-    L.b2v = L.w2v + (int64_t)H * H;
-    L.w1c = L.b2v + H;
-    L.b1c = L.w1c + 2LL * H * H;
-    L.w2c = L.b1c + H;
-    const int proj_nt = LDPC_PROJ_NT != 256 && proj_lds_bytes(types, LDPC_PROJ_NT / 64) <= 160 * 1024 ? LDPC_PROJ_NT : 256;
-    const size_t proj_lds = proj_lds_bytes(types, proj_nt / 64);
-    if (proj_lds > 160 * 1024) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
-    const void *proj_fn = proj_nt != 256 ? reinterpret_cast<const void *>(gnn_group_proj_kernel<LDPC_PROJ_NT>)
-                                         : reinterpret_cast<const void *>(gnn_group_proj_kernel<256>);
-    LDPC_HIP(hipFuncSetAttribute(proj_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)proj_lds));
-    const int per_cu = std::max<int>(1, std::min<int>(3, (int)((160 * 1024) / proj_lds)));
+    set_layer_weights(L, gnn_layer_weights(d_weights, H, types, layer));
+    const ProjKernel k = select_proj(types, false, true, true);
+    if (!k.fits()) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
+    LDPC_HIP(raise_lds(k));
     const ProjTiles T{p->pt_meta, p->pt_grp, p->pt_deg, p->pt_mem, p->n_ptiles, 0};
-    const int64_t ptiles = B * (int64_t)p->n_ptiles;
-    const int pw = proj_nt / 64;
-    const unsigned pgrid = (unsigned)std::min<int64_t>((ptiles + pw - 1) / pw, (int64_t)g_num_cus * per_cu);
-    if (proj_nt != 256)
-        hipLaunchKernelGGL(gnn_group_proj_kernel<LDPC_PROJ_NT>, dim3(pgrid), dim3(LDPC_PROJ_NT), proj_lds, s, L, T);
-    else
-        hipLaunchKernelGGL(gnn_group_proj_kernel<256>, dim3(pgrid), dim3(256), proj_lds, s, L, T);
+    launch(k, B * (int64_t)p->n_ptiles, cus, s, L, T);
     LDPC_CHECK_LAUNCH("gnn_group_proj_kernel (training backward)");
     return LDPC_OK;
 }
@@ -2778,6 +2667,16 @@ extern "C" int64_t ldpc_gnn_custom_var_workspace_size(const ldpc_gnn_plan *p, in
 
 namespace ldpc {
 namespace {
+// The hybrid decoder's GnnLayer (check side alone, every layer with its own output head) and the
+// steps both widths share after a layer's MLP
+GnnLayer hybrid_layer(const ldpc_gnn_plan *p, int H, int types, const float *d_weights, const int32_t *d_msg_type,
+                      const int32_t *d_msg_var, const float *d_llr, int N, int64_t B, const Ws &w) {
+    GnnLayer L = plan_layer(p, H, types, d_weights, d_msg_type, d_msg_var, d_llr, N, B, w.Mv, w.Mc);
+    L.vside = 0; L.residual = 0; L.last = 1; L.d1 = 0;
+    L.msg_out = w.msg_out;
+    return L;
+}
+
 // The hybrid GNN at H != 64 (up to kTiledMaxH): the check side of the generic kernels -- weighted-free
 // group means of the check groups (gnn_group_mean_kernel, vside 0), the tiled MLP over [c; b] with
 // the layer's own output head, then the same variable update and output as H = 64.
@@ -2787,34 +2686,13 @@ int custom_var_forward_any(const ldpc_gnn_plan *p, int H, int types, int layers,
     Ws w = carve(p, H, N, B, std::max(layers, 3), 0, d_work, true);
     float *v2c = reinterpret_cast<float *>(static_cast<char *>(d_work) + w.bytes);
     if (!w.wt) return fail(LDPC_EUNSUPPORTED, "hidden_dim too wide for the hybrid GNN");
-    if (!g_num_cus) {
-        int dev = 0;
-        LDPC_HIP(hipGetDevice(&dev));
-        LDPC_HIP(hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    int cus = 0;
+    if (int rc = gnn_num_cus(&cus)) return rc;
     if (int rc = gnn_build_var_csr(d_msg_var, p->E, N, w.csr, s)) return rc;
-    GnnLayer L{};
-    L.llr = d_llr; L.msg_var = d_msg_var; L.w_in = d_weights; L.b_in = d_weights + H; L.N = N; L.T = types;
-    L.msg_type = d_msg_type;
-    L.vgroup = p->vgroup; L.cgroup = p->cgroup; L.vg_ptr = p->vg_ptr; L.vg_mem = p->vg_mem;
-    L.cg_ptr = p->cg_ptr; L.cg_mem = p->cg_mem; L.inv_v = p->inv_v; L.inv_c = p->inv_c;
-    L.Gv = p->Gv; L.Gc = p->Gc; L.E = p->E; L.B = B; L.Mv = w.Mv; L.Mc = w.Mc;
-    L.vside = 0; L.residual = 0; L.last = 1; L.d1 = 0;
-    L.msg_out = w.msg_out;
+    GnnLayer L = hybrid_layer(p, H, types, d_weights, d_msg_type, d_msg_var, d_llr, N, B, w);
     const int64_t R = B * p->E;
-    const int tw = tiled_waves(H);
-    const size_t tl = (size_t)tw * kTiledNM * 4 * H * 4;
-    if (tl > 64 * 1024)
-        LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gnn_mlp_tiled_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)tl));
-    const float *x_in = nullptr;
     for (int l = 0; l < layers; ++l) {
-        const float *lw = d_weights + 2 * H + (int64_t)l * layer_floats(H, types);
-        L.emb = lw;
-        L.w1v = L.emb + (int64_t)types * H; L.b1v = L.w1v + 2LL * H * H; L.w2v = L.b1v + H; L.b2v = L.w2v + (int64_t)H * H;
-        L.w1c = L.b2v + H; L.b1c = L.w1c + 2LL * H * H; L.w2c = L.b1c + H; L.b2c = L.w2c + (int64_t)H * H;
-        L.wo = L.b2c + H; L.bo = L.wo + H;
-        L.x_in = x_in;
+        set_layer_weights(L, gnn_layer_weights(d_weights, H, types, l));
         L.hv2c = l > 0 ? v2c : nullptr;        // layers >= 1 read x = (v2c w_in + b_in) + F_{l-1}
         L.x_out = (l % 2 == 0) ? w.xa : w.xb;  // F
         L.wt = w.wt + 6LL * H * H * l;
@@ -2824,10 +2702,7 @@ int custom_var_forward_any(const ldpc_gnn_plan *p, int H, int types, int layers,
         const int64_t waves = B * (int64_t)(p->Gv + p->Gc);
         hipLaunchKernelGGL(gnn_group_mean_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, L, H);
         LDPC_CHECK_LAUNCH("gnn_group_mean_kernel (hybrid check side)");
-        const int64_t want = (R + (int64_t)tw * kTiledNM - 1) / ((int64_t)tw * kTiledNM);
-        const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)std::max(1, g_num_cus * 16 / tw));
-        hipLaunchKernelGGL(gnn_mlp_tiled_kernel, dim3(grid), dim3(64 * tw), tl, s, L, H);
-        LDPC_CHECK_LAUNCH("gnn_mlp_tiled_kernel (hybrid check side)");
+        if (int rc = launch_tiled(L, H, R, cus, s, "gnn_mlp_tiled_kernel (hybrid check side)")) return rc;
         hipLaunchKernelGGL(custom_var_llr_kernel, dim3((unsigned)((B * N + 255) / 256)), dim3(256), 0, s, w.msg_out, w.csr,
                            d_llr, p->E, N, B, v2c);
         LDPC_CHECK_LAUNCH("hybrid GNN variable update");
@@ -2836,7 +2711,7 @@ int custom_var_forward_any(const ldpc_gnn_plan *p, int H, int types, int layers,
                                v2c, d_weights, d_weights + H, H, R, L.wo, L.bo, w.msg_out);
             LDPC_CHECK_LAUNCH("hybrid GNN output head");
         }
-        x_in = L.x_out;
+        L.x_in = L.x_out;
     }
     hipLaunchKernelGGL(custom_output_kernel, dim3((unsigned)((B * N + 255) / 256)), dim3(256), 0, s, w.msg_out, w.csr, d_llr,
                        p->E, N, B * N, d_probs);
@@ -2866,55 +2741,24 @@ extern "C" int ldpc_gnn_custom_var_forward(const ldpc_gnn_plan *p, int hidden, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     Ws w = carve(p, H, N, B, std::max(layers, 3), 0, d_work);
     float *v2c = reinterpret_cast<float *>(static_cast<char *>(d_work) + w.bytes);
-    if (!g_num_cus) {
-        int dev = 0;
-        LDPC_HIP(hipGetDevice(&dev));
-        LDPC_HIP(hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    const bool split = split_path() && mlp2s_lds_bytes(types, false) <= 160 * 1024;
-    const size_t proj_lds = proj_lds_bytes(types, 4), mlp2_lds = split ? mlp2s_lds_bytes(types, false) : mlp2_lds_bytes(types);
-    if (proj_lds > 160 * 1024 || mlp2_lds > 160 * 1024) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
-    LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gnn_group_proj_kernel<256, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)proj_lds));
-    LDPC_HIP(hipFuncSetAttribute(split ? reinterpret_cast<const void *>(gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, true>)
-                                       : reinterpret_cast<const void *>(gnn_mlp2_kernel<kMlp2Nt, kMlp2Wps, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp2_lds));
-    const int mlp2_per_cu = std::max<int>(1, std::min<int>(4 * kMlp2Wps / (kMlp2Nt / 64), (int)((160 * 1024) / mlp2_lds)));
-    const int proj_per_cu = std::max<int>(1, std::min<int>(3, (int)((160 * 1024) / proj_lds)));
+    int cus = 0;
+    if (int rc = gnn_num_cus(&cus)) return rc;
+    const ProjKernel proj_k = select_proj(types, true, true, true);
+    const MlpKernel mlp_k = select_mlp(types, true, split_on(types, false), false, false, false);
+    if (!proj_k.fits() || !mlp_k.fits()) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
+    LDPC_HIP(raise_lds(proj_k));
+    LDPC_HIP(raise_lds(mlp_k));
     if (int rc = gnn_build_var_csr(d_msg_var, p->E, N, w.csr, s)) return rc;
-    GnnLayer L{};
-    L.llr = d_llr; L.msg_var = d_msg_var; L.w_in = d_weights; L.b_in = d_weights + H; L.N = N; L.T = types;
-    L.msg_type = d_msg_type;
-    L.vgroup = p->vgroup; L.cgroup = p->cgroup; L.vg_ptr = p->vg_ptr; L.vg_mem = p->vg_mem;
-    L.cg_ptr = p->cg_ptr; L.cg_mem = p->cg_mem; L.inv_v = p->inv_v; L.inv_c = p->inv_c;
-    L.Gv = p->Gv; L.Gc = p->Gc; L.E = p->E; L.B = B; L.Mv = w.Mv; L.Mc = w.Mc;
-    L.vside = 0; L.residual = 0; L.last = 1; L.d1 = 0;
-    L.msg_out = w.msg_out;
+    GnnLayer L = hybrid_layer(p, H, types, d_weights, d_msg_type, d_msg_var, d_llr, N, B, w);
     const ProjTiles T{p->pt_meta, p->pt_grp, p->pt_deg, p->pt_mem, p->n_ptiles, p->n_ptiles_v};
     const int64_t R = B * p->E;
-    const float *x_in = nullptr;
     for (int l = 0; l < layers; ++l) {
-        const float *lw = d_weights + 2 * H + (int64_t)l * layer_floats(H, types);
-        L.emb = lw;
-        L.w1v = L.emb + (int64_t)types * H; L.b1v = L.w1v + 2LL * H * H; L.w2v = L.b1v + H; L.b2v = L.w2v + (int64_t)H * H;
-        L.w1c = L.b2v + H; L.b1c = L.w1c + 2LL * H * H; L.w2c = L.b1c + H; L.b2c = L.w2c + (int64_t)H * H;
-        L.wo = L.b2c + H; L.bo = L.wo + H;
-        L.x_in = x_in;
+        set_layer_weights(L, gnn_layer_weights(d_weights, H, types, l));
         L.hv2c = l > 0 ? v2c : nullptr;        // layers >= 1 read x = (v2c w_in + b_in) + F_{l-1}
         L.x_out = (l % 2 == 0) ? w.xa : w.xb;  // F
-        const int64_t ptiles = B * (int64_t)(T.n_tiles - T.first);
-        hipLaunchKernelGGL((gnn_group_proj_kernel<256, true>), dim3((unsigned)std::min<int64_t>((ptiles + 3) / 4, (int64_t)g_num_cus * proj_per_cu)),
-                           dim3(256), proj_lds, s, L, T);
+        launch(proj_k, B * (int64_t)(T.n_tiles - T.first), cus, s, L, T);
         LDPC_CHECK_LAUNCH("gnn_group_proj_kernel (check side)");
-        constexpr int wpb = kMlp2Nt / 64;
-        const int64_t tiles = (R + 31) / 32;
-        const dim3 mgrid((unsigned)std::min<int64_t>((tiles + wpb - 1) / wpb, (int64_t)g_num_cus * mlp2_per_cu));
-        if (split)
-            hipLaunchKernelGGL((gnn_mlp2s_kernel<kMlp2sNt, kMlp2sWps, true>),
-                               dim3((unsigned)std::min<int64_t>((tiles + kMlp2sNt / 64 - 1) / (kMlp2sNt / 64), (int64_t)g_num_cus)),
-                               dim3(kMlp2sNt), mlp2_lds, s, L);
-        else
-            hipLaunchKernelGGL((gnn_mlp2_kernel<kMlp2Nt, kMlp2Wps, true>), mgrid, dim3(kMlp2Nt), mlp2_lds, s, L);
+        launch(mlp_k, (R + 31) / 32, cus, s, L);
         LDPC_CHECK_LAUNCH("gnn_mlp2_kernel (check side)");
         hipLaunchKernelGGL(custom_var_llr_kernel, dim3((unsigned)((B * N + 255) / 256)), dim3(256), 0, s, w.msg_out, w.csr,
                            d_llr, p->E, N, B, v2c);
@@ -2923,7 +2767,7 @@ extern "C" int ldpc_gnn_custom_var_forward(const ldpc_gnn_plan *p, int hidden, i
             hipLaunchKernelGGL(custom_combine_kernel, dim3((unsigned)((R * 16 + 255) / 256)), dim3(256), 0, s, L.x_out,
                                v2c, d_weights, d_weights + H, R, L.wo, L.bo, w.msg_out);
         LDPC_CHECK_LAUNCH("hybrid GNN output head");
-        x_in = L.x_out;
+        L.x_in = L.x_out;
     }
     hipLaunchKernelGGL(custom_output_kernel, dim3((unsigned)((B * N + 255) / 256)), dim3(256), 0, s, w.msg_out, w.csr, d_llr,
                        p->E, N, B * N, d_probs);

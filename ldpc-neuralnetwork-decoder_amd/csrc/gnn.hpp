@@ -73,6 +73,42 @@ struct ldpc_gnn_plan {
 
 namespace ldpc {
 
+// The weight blob (ldpc_amd.h): w_in (H), b_in (H), then per layer the eleven sections below, in this
+// order.  This is the one statement of that layout: every reader of the blob, host or device, and the
+// trainer's gradient blob (P = float *) go through gnn_layer_weights.
+template <typename P>
+struct GnnLayerWeights {
+    P emb;       // (T, H)
+    P w1v, b1v;  // (H, 2H), (H)
+    P w2v, b2v;  // (H, H), (H)
+    P w1c, b1c, w2c, b2c;
+    P wo, bo;    // (H), (1)
+};
+__host__ __device__ inline int64_t gnn_layer_floats(int H, int T) {
+    const int64_t h = H;
+    return T * h + 2 * (2 * h * h + h + h * h + h) + h + 1;
+}
+template <typename P>
+__host__ __device__ inline GnnLayerWeights<P> gnn_layer_weights(P blob, int H, int T, int l) {
+    const int64_t h = H;
+    GnnLayerWeights<P> w;
+    w.emb = blob + 2 * h + l * gnn_layer_floats(H, T);
+    w.w1v = w.emb + T * h;
+    w.b1v = w.w1v + 2 * h * h;
+    w.w2v = w.b1v + h;
+    w.b2v = w.w2v + h * h;
+    w.w1c = w.b2v + h;
+    w.b1c = w.w1c + 2 * h * h;
+    w.w2c = w.b1c + h;
+    w.b2c = w.w2c + h * h;
+    w.wo = w.b2c + h;
+    w.bo = w.wo + h;
+    return w;
+}
+
+// The current device's compute-unit count, queried once per process (gnn.hip)
+int gnn_num_cus(int *cus);
+
 // Deterministic output stage (message_gnn_decoder.py:277-307).  The last layer writes each
 // message's projected LLR into msg_out (B, E); every variable then sums its messages in ascending
 // message order, as the reference's loop does, from a per-call CSR of msg_var (gnn.hip).
@@ -116,7 +152,7 @@ struct GnnWideLayer {
     const float *llr;
     const int32_t *msg_type, *msg_var;
     const float *w_in, *b_in;
-    const float *emb, *w1v, *b1v, *w2v, *b2v, *w1c, *b1c, *w2c, *b2c, *wo, *bo;
+    GnnLayerWeights<const float *> w;
     float *Mv, *Mc, *Pv, *Pc, *hbuf, *y;
     int residual;
     float *msg_out;
@@ -140,9 +176,9 @@ int gnn_wide_layer(const GnnWideLayer &L, hipStream_t s);
 int64_t gnn_wide_fused_bytes(int H, int layers);
 bool gnn_wide_fused_fits(int H, int T);
 // every layer's mean type embedding per var / check group (the group-mean pass adds it once)
-int gnn_wide_memb(const ldpc_gnn_plan *p, int H, int layers, const float *emb0, int64_t layer_stride,
-                  const int32_t *msg_type, float *memb, hipStream_t s);
-int gnn_wide_prep(int H, int layers, const float *blob, int64_t layer_floats, int T, char *wimg, int *wexp, hipStream_t s);
+int gnn_wide_memb(const ldpc_gnn_plan *p, int H, int T, int layers, const float *blob, const int32_t *msg_type,
+                  float *memb, hipStream_t s);
+int gnn_wide_prep(int H, int layers, const float *blob, int T, char *wimg, int *wexp, hipStream_t s);
 
 // The per-device side stream and the calling thread's fork/join events the forwards split their
 // frames over (thread-safe: see gnn.hip).
@@ -218,13 +254,9 @@ typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 // v1 = f16(v - v0) as one v_fma_mixlo / mixhi_f16 per value: fma(-v0, 1, v) with v0 read as f16
 // straight from the packed pair and rounded once to f16 -- the same value as converting v0 back,
 // subtracting in f32 (exact: v0 is v rounded) and converting again (tools/ubench/split_mix.hip,
-// 2^23 pairs bit for bit), in 12 instead of ~24 VALU per 8 values.  LDPC_SPLIT_MIX=0: that form.
-#ifndef LDPC_SPLIT_MIX
-#define LDPC_SPLIT_MIX 1
-#endif
+// 2^23 pairs bit for bit), in 12 instead of ~24 VALU per 8 values.
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split2h(const float *v, f16x8_t &a, f16x8_t &b) {
-#if LDPC_SPLIT_MIX
     uint32_t hi[4], lo[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
@@ -237,14 +269,6 @@ __device__ __forceinline__ void split2h(const float *v, f16x8_t &a, f16x8_t &b) 
     }
     a = __builtin_bit_cast(f16x8_t, hi);
     b = __builtin_bit_cast(f16x8_t, lo);
-#else
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const _Float16 h0 = (_Float16)v[i];
-        a[i] = h0;
-        b[i] = (_Float16)(v[i] - (float)h0);
-    }
-#endif
 }
 __device__ __forceinline__ void split2h_store(float w, _Float16 *d, int stride) {
     const _Float16 h0 = (_Float16)w;

@@ -57,26 +57,6 @@ __host__ __device__ constexpr int acc_unit(int a) {
     return 32 * (a >> 5) + (a & 3) + 8 * ((a >> 2) & 3) + 4 * ((a >> 4) & 1);
 }
 
-struct LayerW {
-    const float *emb, *w1v, *b1v, *w2v, *b2v, *w1c, *b1c, *w2c, *b2c, *wo, *bo;
-};
-__host__ __device__ inline int64_t layer_floats(int T) { return (int64_t)T * H + 2 * (2 * H * H + H + H * H + H) + H + 1; }
-__host__ __device__ inline LayerW layer_w(const float *blob, int T, int l) {
-    LayerW w;
-    w.emb = blob + 2 * H + (int64_t)l * layer_floats(T);
-    w.w1v = w.emb + (int64_t)T * H;
-    w.b1v = w.w1v + 2 * H * H;
-    w.w2v = w.b1v + H;
-    w.b2v = w.w2v + H * H;
-    w.w1c = w.b2v + H;
-    w.b1c = w.w1c + 2 * H * H;
-    w.w2c = w.b1c + H;
-    w.b2c = w.w2c + H * H;
-    w.wo = w.b2c + H;
-    w.bo = w.wo + H;
-    return w;
-}
-
 // derived constants per layer (floats): K[T + 2][2 sides][64 acc order] (rows T, T+1 = U, V of
 // layer 0), then b2v + b2c [64 acc], wo [64 acc], then D1[T][64 acc] = K[t][var side] +
 // W1_v,right emb[t] (degree-1 var groups)
@@ -86,7 +66,7 @@ __host__ __device__ inline int64_t kd_d1(int T) { return (int64_t)(T + 3) * 128;
 __global__ __launch_bounds__(128) void gnn_bf16_kconst_kernel(const float *blob, int T, float *kd) {
     const int l = blockIdx.x, t = blockIdx.y, side = threadIdx.x >> 6, a = threadIdx.x & 63;
     const int u = acc_unit(a);
-    const LayerW w = layer_w(blob, T, l);
+    const auto w = gnn_layer_weights(blob, H, T, l);
     const float *W1 = (side ? w.w1c : w.w1v) + u * 2 * H;  // row u, left half = columns 0..63
     const float *v = t < T ? w.emb + t * H : t == T ? blob : blob + H;  // emb[t] | w_in | b_in
     float s = t < T ? (side ? w.b1c : w.b1v)[u] : 0.0f;
@@ -148,7 +128,7 @@ __global__ __launch_bounds__(256) void gnn_bf16_memb_kernel(const float *blob, i
     const int g = G.grp[8 * t + q];
     if (g < 0) return;
     const int2 md = G.meta[t];
-    const float *emb = layer_w(blob, T, l).emb;
+    const float *emb = gnn_layer_weights(blob, H, T, l).emb;
     float acc[8] = {};
     for (int i = 0; i < md.x; ++i) {
         const float *e = emb + msg_type[G.mem[md.y + 8 * i + q]] * H;
@@ -277,10 +257,7 @@ constexpr int kOffK = 2 * kW1B + 2 * kW2B;
 constexpr int kKStride = 132;
 // D1 rows: 68 floats apart (a row stride of 64 put every type's row on the same LDS banks: the
 // 16-lane groups of a ds_read_b128 with lanes of different types serialised up to 16-way)
-#ifndef LDPC_BF16_D1_STRIDE
-#define LDPC_BF16_D1_STRIDE 68
-#endif
-constexpr int kD1Stride = LDPC_BF16_D1_STRIDE;
+constexpr int kD1Stride = 68;
 // then (MODE bit 2) one 4 KB staging tile per wave for the in-tile check sums
 constexpr int kCTileB = 32 * 128;
 __host__ __device__ inline size_t mlp_tables_bytes(int T, bool d1) {
@@ -751,15 +728,13 @@ Bf16Ws carve_bf16(const ldpc_gnn_plan *p, int N, int64_t B, int T, int L, void *
     return w;
 }
 
-int g_cus = 0;
-
 template <int MODE>
-int launch_mlp_t(int64_t tiles, size_t lds, hipStream_t s, const MlpArgs &m) {
+int launch_mlp_t(int64_t tiles, size_t lds, int cus, hipStream_t s, const MlpArgs &m) {
     const void *fn = reinterpret_cast<const void *>(gnn_bf16_mlp_kernel<MODE>);
     LDPC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int per_cu = 4 * 2 / (kMlpThreads / 64);  // workgroups per CU at 2 waves per SIMD
     const unsigned grid = (unsigned)std::min<int64_t>((tiles + kMlpThreads / 64 - 1) / (kMlpThreads / 64),
-                                                      (int64_t)g_cus * per_cu);
+                                                      (int64_t)cus * per_cu);
     hipLaunchKernelGGL((gnn_bf16_mlp_kernel<MODE>), dim3(grid), dim3(kMlpThreads), lds, s, m);
     return LDPC_OK;
 }
@@ -767,14 +742,14 @@ int launch_mlp_t(int64_t tiles, size_t lds, hipStream_t s, const MlpArgs &m) {
 // the MLP kernel per layer mode (bit 0 layer 0, bit 1 last layer, bit 2 in-tile check means): one
 // 512-thread workgroup per CU, 2 waves per SIMD, next tile prefetched into registers (measured
 // against 3-4 waves per SIMD and deeper prefetch: all within 2 % or slower)
-int launch_mlp(int mode, int64_t tiles, size_t lds, hipStream_t s, const MlpArgs &m) {
+int launch_mlp(int mode, int64_t tiles, size_t lds, int cus, hipStream_t s, const MlpArgs &m) {
     switch (mode) {
-        case 0: return launch_mlp_t<0>(tiles, lds, s, m);
-        case 1: return launch_mlp_t<1>(tiles, lds, s, m);
-        case 2: return launch_mlp_t<2>(tiles, lds, s, m);
-        case 3: return launch_mlp_t<3>(tiles, lds, s, m);
-        case 4: return launch_mlp_t<4>(tiles, lds, s, m);
-        case 6: return launch_mlp_t<6>(tiles, lds, s, m);
+        case 0: return launch_mlp_t<0>(tiles, lds, cus, s, m);
+        case 1: return launch_mlp_t<1>(tiles, lds, cus, s, m);
+        case 2: return launch_mlp_t<2>(tiles, lds, cus, s, m);
+        case 3: return launch_mlp_t<3>(tiles, lds, cus, s, m);
+        case 4: return launch_mlp_t<4>(tiles, lds, cus, s, m);
+        case 6: return launch_mlp_t<6>(tiles, lds, cus, s, m);
         default: return fail(LDPC_EINVAL, "bad MLP mode");
     }
 }
@@ -828,11 +803,8 @@ int gnn_bf16_forward(const ldpc_gnn_plan *p, int T, int L, const float *d_weight
     const size_t lds = mlp_lds_bytes(T, d1);
     if (T > kBf16MaxTypes || lds > 160 * 1024)
         return fail(LDPC_EUNSUPPORTED, "too many message types for the bf16 LDS image");
-    if (!g_cus) {
-        int dev = 0;
-        LDPC_HIP(hipGetDevice(&dev));
-        LDPC_HIP(hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    int cus = 0;
+    if (int rc = gnn_num_cus(&cus)) return rc;
     const GtArgs G{p->gt_meta, p->gt_grp, p->gt_mem, p->n_gtiles, 0};
     const int Gtot = p->Gv + p->Gc;
     {
@@ -860,7 +832,7 @@ int gnn_bf16_forward(const ldpc_gnn_plan *p, int T, int L, const float *d_weight
     }
     const uint8_t *active = et ? w.active : nullptr;
     const float *kd_last = w.kd + (int64_t)(L - 1) * kd_floats(T);
-    const float *bo_last = layer_w(d_weights, T, L - 1).bo;
+    const float *bo_last = gnn_layer_weights(d_weights, H, T, L - 1).bo;
 
     // frames [b0, b0 + nb) through every layer on stream st (pointers offset to the range)
     auto run_range = [&](int64_t b0, int64_t nb, hipStream_t st, int slot) -> int {
@@ -874,7 +846,7 @@ int gnn_bf16_forward(const ldpc_gnn_plan *p, int T, int L, const float *d_weight
     bool listed = false;  // after the first syndrome pass the kernels walk the active list
     const __bf16 *x_in = nullptr;
     for (int l = 0; l < L; ++l) {
-        const LayerW lw = layer_w(d_weights, T, l);
+        const auto lw = gnn_layer_weights(d_weights, H, T, l);
         // layers >= 1 on check-aligned tiles: the MLP forms the check means itself, the group-mean
         // pass does the var groups alone (layer 0's means come from the LLRs: both sides here)
         const bool itc = p->ct_aligned && l > 0;
@@ -901,7 +873,7 @@ int gnn_bf16_forward(const ldpc_gnn_plan *p, int T, int L, const float *d_weight
         if (gm.G.n_tiles > gm.G.first) {
             const int64_t gwaves = nb * (gm.G.n_tiles - gm.G.first);
             int64_t gblocks = (gwaves + 3) / 4;
-            if (gm.count && gm_cap() > 0) gblocks = std::min<int64_t>(gblocks, (int64_t)g_cus * gm_cap());
+            if (gm.count && gm_cap() > 0) gblocks = std::min<int64_t>(gblocks, (int64_t)cus * gm_cap());
             hipLaunchKernelGGL(gnn_bf16_gm_kernel, dim3((unsigned)gblocks), dim3(256), 0, st, gm);
             LDPC_CHECK_LAUNCH("gnn_bf16_gm_kernel");
         }
@@ -937,7 +909,7 @@ int gnn_bf16_forward(const ldpc_gnn_plan *p, int T, int L, const float *d_weight
         m.kd_last = et && l < L - 1 ? kd_last : nullptr;
         m.bo_last = bo_last;
         const int mode = (l == 0 ? 1 : 0) | (l == L - 1 ? 2 : 0) | (itc ? 4 : 0);
-        const int rc = launch_mlp(mode, nb * tpf, lds, st, m);
+        const int rc = launch_mlp(mode, nb * tpf, lds, cus, st, m);
         if (rc != LDPC_OK) return rc;
         LDPC_CHECK_LAUNCH("gnn_bf16_mlp_kernel");
         if (m.kd_last) {

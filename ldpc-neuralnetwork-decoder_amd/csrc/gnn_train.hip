@@ -46,28 +46,6 @@ constexpr int kMaxH = 64;         // widest H of the LDS-image kernels (train_ml
 // recomputes exactly those products, so hv and the ReLU masks it rebuilds are the forward's bit for bit
 constexpr int kMaxTrainH = 1024;
 
-struct TW {  // one layer's weights in the blob (see ldpc_amd.h)
-    const float *emb, *w1v, *b1v, *w2v, *b2v, *w1c, *b1c, *w2c, *b2c, *wo, *bo;
-};
-__host__ __device__ inline int64_t tl_floats(int H, int T) {
-    return (int64_t)T * H + 2 * (2LL * H * H + H + (int64_t)H * H + H) + H + 1;
-}
-template <typename P>
-__host__ __device__ inline void t_layer(P blob, int H, int T, int l, P *out) {  // 11 section pointers
-    P e = blob + 2 * H + (int64_t)l * tl_floats(H, T);
-    out[0] = e;                           // emb
-    out[1] = out[0] + (int64_t)T * H;     // w1v
-    out[2] = out[1] + 2LL * H * H;        // b1v
-    out[3] = out[2] + H;                  // w2v
-    out[4] = out[3] + (int64_t)H * H;     // b2v
-    out[5] = out[4] + H;                  // w1c
-    out[6] = out[5] + 2LL * H * H;        // b1c
-    out[7] = out[6] + H;                  // w2c
-    out[8] = out[7] + (int64_t)H * H;     // b2c
-    out[9] = out[8] + H;                  // wo
-    out[10] = out[9] + H;                 // bo
-}
-
 // ------------------------------------------------------------------------ head
 __global__ void train_head_kernel(const float *__restrict__ p, const float *__restrict__ g, int64_t n,
                                   float *__restrict__ dz) {
@@ -1711,7 +1689,6 @@ TrainWs carve_train(const ldpc_gnn_plan *p, int H, int N, int64_t B, void *base)
     return w;
 }
 
-int g_cus_t = 0;
 
 // per-device, per-thread events of the backward's side-stream recompute (see bwd_overlap)
 int train_events(hipEvent_t ready[2], hipEvent_t freed[2]) {
@@ -1818,17 +1795,14 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
         return fail(LDPC_EINVAL, "d_layer_probs and d_grad_layer_probs go together");
     const bool ds = d_layer_probs != nullptr && L > 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t wfloats = 2LL * H + (int64_t)L * tl_floats(H, T);
+    const int64_t wfloats = 2LL * H + (int64_t)L * gnn_layer_floats(H, T);
     LDPC_HIP(hipMemsetAsync(d_grad_weights, 0, (size_t)wfloats * 4, s));
     if (B == 0) return LDPC_OK;
     TrainWs w = carve_train(p, H, N, B, d_work);
     if (!d_work || work_bytes < w.bytes)
         return fail(LDPC_EINVAL, "workspace too small: need " + std::to_string(w.bytes) + " bytes");
-    if (!g_cus_t) {
-        int dev = 0;
-        LDPC_HIP(hipGetDevice(&dev));
-        LDPC_HIP(hipDeviceGetAttribute(&g_cus_t, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    int cus = 0;
+    if (int rc = gnn_num_cus(&cus)) return rc;
     const int64_t E = p->E, R = B * E, n = R * H;
     const size_t lds_mlp = mlp_bwd_lds(H);
     // H > 64: train_mlp_bwd_wide_kernel with as many waves per workgroup (<= 4) as its LDS rows allow
@@ -1854,16 +1828,14 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_bwd_s6_lds()));
     }
     auto blocks = [](int64_t work, int per) { return dim3((unsigned)((work + per - 1) / per)); };
-    const unsigned red_grid = (unsigned)std::min<int64_t>((R + 63) / 64, (int64_t)g_cus_t * kOuterWgs);
+    const unsigned red_grid = (unsigned)std::min<int64_t>((R + 63) / 64, (int64_t)cus * kOuterWgs);
 
     // head: dz, dX_L, dwo, dbo
-    const float *WL[11];
-    t_layer(d_weights, H, T, L - 1, WL);
-    float *GL[11];
-    t_layer(d_grad_weights, H, T, L - 1, GL);
+    const auto WL = gnn_layer_weights(d_weights, H, T, L - 1);
+    const auto GL = gnn_layer_weights(d_grad_weights, H, T, L - 1);
     hipLaunchKernelGGL(train_head_kernel, blocks(B * N, 256), dim3(256), 0, s, d_probs, d_grad_probs, B * N, w.dz);
     LDPC_CHECK_LAUNCH("train_head_kernel");
-    hipLaunchKernelGGL(train_dx_last_kernel, blocks(n, 256), dim3(256), 0, s, w.dz, d_msg_var, WL[9], H, E, N, n,
+    hipLaunchKernelGGL(train_dx_last_kernel, blocks(n, 256), dim3(256), 0, s, w.dz, d_msg_var, WL.wo, H, E, N, n,
                        w.dX, 0);
     LDPC_CHECK_LAUNCH("train_dx_last_kernel");
     {
@@ -1873,8 +1845,8 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
         v.dz = w.dz;
         v.msg_type = d_msg_type;
         v.msg_var = d_msg_var;
-        v.g0 = GL[9];
-        v.g1 = GL[10];
+        v.g0 = GL.wo;
+        v.g1 = GL.bo;
         v.H = H; v.T = T; v.N = N; v.mode = 2; v.E = E; v.R = R;
         if (int rc = launch_vec(v, w.hv, w.hc, s)) return rc;
     }
@@ -1902,21 +1874,19 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
     // on s2 may still write the caller's workspace once the caller's stream moves on
     auto layers_back = [&]() -> int {
     for (int l = L - 1; l >= 0; --l) {
-        const float *W[11];
-        t_layer(d_weights, H, T, l, W);
-        float *Gw[11];
-        t_layer(d_grad_weights, H, T, l, Gw);
+        const auto W = gnn_layer_weights(d_weights, H, T, l);
+        const auto Gw = gnn_layer_weights(d_grad_weights, H, T, l);
         if (ds && l < L - 1) {  // deep supervision: layer l's output through the last layer's head
             const float *pl = d_layer_probs + (int64_t)l * B * N, *gl = d_grad_layer_probs + (int64_t)l * B * N;
             hipLaunchKernelGGL(train_head_kernel, blocks(B * N, 256), dim3(256), 0, s, pl, gl, B * N, w.dz);
             LDPC_CHECK_LAUNCH("train_head_kernel");
-            hipLaunchKernelGGL(train_dx_last_kernel, blocks(n, 256), dim3(256), 0, s, w.dz, d_msg_var, WL[9], H, E, N,
+            hipLaunchKernelGGL(train_dx_last_kernel, blocks(n, 256), dim3(256), 0, s, w.dz, d_msg_var, WL.wo, H, E, N,
                                n, w.dX, 1);
             LDPC_CHECK_LAUNCH("train_dx_last_kernel");
             VecT v{};
             v.part = w.dhv; v.part_cap = R * H;
             v.src = d_saved + (int64_t)l * n;
-            v.dz = w.dz; v.msg_type = d_msg_type; v.msg_var = d_msg_var; v.g0 = GL[9]; v.g1 = GL[10];
+            v.dz = w.dz; v.msg_type = d_msg_type; v.msg_var = d_msg_var; v.g0 = GL.wo; v.g1 = GL.bo;
             v.H = H; v.T = T; v.N = N; v.mode = 2; v.E = E; v.R = R;
             if (int rc = launch_vec(v, w.hv, w.hc, s)) return rc;
         }
@@ -1951,7 +1921,7 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
                 return rc;
         } else {  // group means of c (forward recompute)
             GmT g{};
-            g.src = x; g.emb = W[0]; g.llr = d_llr; g.w_in = d_weights; g.b_in = d_weights + H;
+            g.src = x; g.emb = W.emb; g.llr = d_llr; g.w_in = d_weights; g.b_in = d_weights + H;
             g.msg_type = d_msg_type; g.msg_var = d_msg_var;
             g.src_mode = x ? 1 : 2; g.H = H; g.N = N; g.E = E; g.B = B;
             g.ptr = p->vg_ptr; g.mem = p->vg_mem; g.inv = p->inv_v; g.G = p->Gv; g.dst = w.Mv; g.w = p->vg_w;
@@ -1964,13 +1934,13 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
         m.x = x; m.llr = d_llr; m.w_in = d_weights; m.b_in = d_weights + H;
         m.Mv = Pv; m.Mc = Pc; m.dX = w.dX;
         m.msg_type = d_msg_type; m.msg_var = d_msg_var; m.vgroup = p->vgroup; m.cgroup = p->cgroup;
-        m.emb = W[0]; m.w1v = W[1]; m.b1v = W[2]; m.w2v = W[3]; m.w1c = W[5]; m.b1c = W[6]; m.w2c = W[7];
+        m.emb = W.emb; m.w1v = W.w1v; m.b1v = W.b1v; m.w2v = W.w2v; m.w1c = W.w1c; m.b1c = W.b1c; m.w2c = W.w2c;
         m.cbuf = pj ? nullptr : w.cbuf;  // PJ: train_dw1_kernel forms c itself
         m.hv = w.hv; m.hc = w.hc; m.dhv = w.dhv; m.dhc = w.dhc;
         m.dco = w.dco; m.da = w.da; m.db = w.db;
         m.H = H; m.N = N; m.Gv = p->Gv; m.Gc = p->Gc; m.E = E; m.R = R;
         if (H == 64) {  // fp32 MFMA / split MFMA kernels, 8 waves per workgroup
-            const unsigned grid = (unsigned)std::min<int64_t>((R + 32 * 8 - 1) / (32 * 8), (int64_t)g_cus_t);
+            const unsigned grid = (unsigned)std::min<int64_t>((R + 32 * 8 - 1) / (32 * 8), (int64_t)cus);
             if (pj && bwd_s6())
                 hipLaunchKernelGGL(train_mlp_bwd_s6_kernel, dim3(grid), dim3(512), mlp_bwd_s6_lds(), s, m);
             else if (pj)
@@ -1980,12 +1950,12 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
             LDPC_CHECK_LAUNCH("train_mlp_bwd_mfma_kernel");
         } else if (H > kMaxH) {
             const int rows = wide_waves * kNM;
-            const unsigned mgrid = (unsigned)std::min<int64_t>((R + rows - 1) / rows, (int64_t)g_cus_t * 8 / wide_waves);
+            const unsigned mgrid = (unsigned)std::min<int64_t>((R + rows - 1) / rows, (int64_t)cus * 8 / wide_waves);
             hipLaunchKernelGGL(train_mlp_bwd_wide_kernel, dim3(mgrid), dim3(64 * wide_waves), mlp_bwd_wide_lds(H, wide_waves),
                                s, m);
             LDPC_CHECK_LAUNCH("train_mlp_bwd_wide_kernel");
         } else {
-            const unsigned mgrid = (unsigned)std::min<int64_t>((R + 4 * kNM - 1) / (4 * kNM), (int64_t)g_cus_t * 2);
+            const unsigned mgrid = (unsigned)std::min<int64_t>((R + 4 * kNM - 1) / (4 * kNM), (int64_t)cus * 2);
             hipLaunchKernelGGL(train_mlp_bwd_kernel, dim3(mgrid), dim3(256), lds_mlp, s, m);
             LDPC_CHECK_LAUNCH("train_mlp_bwd_kernel");
         }
@@ -2000,8 +1970,8 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
                 if (int rc = launch_group_mean(gs, s)) return rc;
             }
             const int64_t gtiles = (B * std::max(p->Gv, p->Gc) + 31) / 32;
-            const unsigned ggrid = (unsigned)std::min<int64_t>((gtiles + 3) / 4, (int64_t)g_cus_t * 4);
-            hipLaunchKernelGGL(train_group_back_kernel, dim3(ggrid), dim3(256), 0, s, Mv, Mc, W[1], W[5], p->inv_v,
+            const unsigned ggrid = (unsigned)std::min<int64_t>((gtiles + 3) / 4, (int64_t)cus * 4);
+            hipLaunchKernelGGL(train_group_back_kernel, dim3(ggrid), dim3(256), 0, s, Mv, Mc, W.w1v, W.w1c, p->inv_v,
                                p->inv_c, p->Gv, p->Gc, B, w.Mda, w.Mdb);
             LDPC_CHECK_LAUNCH("train_group_back_kernel");
         } else {
@@ -2033,13 +2003,13 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
         OuterT o{};
         o.H = H; o.E = E; o.R = R;
         if (H == 64) {  // dW2v and dW2c in one pass over dX
-            Dw2T d2{w.dX, w.hv, w.hc, Gw[3], Gw[7], Gw[4], Gw[8], R};
+            Dw2T d2{w.dX, w.hv, w.hc, Gw.w2v, Gw.w2c, Gw.b2v, Gw.b2c, R};
             hipLaunchKernelGGL(train_dw2_kernel, dim3(red_grid), dim3(256), 0, s, d2);
             LDPC_CHECK_LAUNCH("train_dw2_kernel");
         } else {  // general H: two passes
-            o.A = w.dX; o.zsrc = w.hv; o.J = H; o.out = Gw[3]; o.bias = Gw[4];
+            o.A = w.dX; o.zsrc = w.hv; o.J = H; o.out = Gw.w2v; o.bias = Gw.b2v;
             if (int rc = launch_outer(o, red_grid, s)) return rc;
-            o.zsrc = w.hc; o.out = Gw[7]; o.bias = Gw[8];
+            o.zsrc = w.hc; o.out = Gw.w2c; o.bias = Gw.b2c;
             if (int rc = launch_outer(o, red_grid, s)) return rc;
         }
         // dW1_s = sum_m dh_s[m] (x) [c_m; g_s(group(m))]: the c half row by row; the group half as
@@ -2047,9 +2017,9 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
         // a gathered group row per message (Mda / Mdb are free again after the combine step)
         if (pj) {  // the c half of both sides in one pass, c formed from x (no stored copy)
             Dw1T d{};
-            d.dhv = w.dhv; d.dhc = w.dhc; d.x = x; d.emb = W[0]; d.llr = d_llr;
+            d.dhv = w.dhv; d.dhc = w.dhc; d.x = x; d.emb = W.emb; d.llr = d_llr;
             d.w_in = d_weights; d.b_in = d_weights + H; d.msg_type = d_msg_type; d.msg_var = d_msg_var;
-            d.gv = Gw[1]; d.gc = Gw[5]; d.bv = Gw[2]; d.bc = Gw[6];
+            d.gv = Gw.w1v; d.gc = Gw.w1c; d.bv = Gw.b1v; d.bc = Gw.b1c;
             d.T = T; d.N = N; d.E = E; d.R = R;
             if (x)
                 hipLaunchKernelGGL(train_dw1_kernel<1>, dim3(red_grid), dim3(256), dw1_lds(T), s, d);
@@ -2061,7 +2031,7 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
             // PJ: the group means are in Gsv / Gsc and the group sums of dh already in Mv / Mc
             const float *dh = side ? w.dhc : w.dhv, *Gs = pj ? (side ? Gsc : Gsv) : side ? w.Mc : w.Mv;
             float *dhsum = pj ? (side ? Mc : Mv) : side ? w.Mdb : w.Mda;
-            float *gw = side ? Gw[5] : Gw[1], *gb = side ? Gw[6] : Gw[2];
+            float *gw = side ? Gw.w1c : Gw.w1v, *gb = side ? Gw.b1c : Gw.b1v;
             const int Gn = side ? p->Gc : p->Gv;
             if (!pj) {
                 OuterT c{};
@@ -2079,7 +2049,7 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
             OuterT g{};
             g.H = H; g.E = (int64_t)Gn; g.R = B * Gn; g.A = p->weighted ? dh : dhsum; g.zsrc = Gs; g.J = H; g.ld = 2 * H; g.col0 = H;
             g.out = gw; g.bias = nullptr;
-            const unsigned ggrid = (unsigned)std::min<int64_t>((g.R + 63) / 64, (int64_t)g_cus_t * kOuterWgs);
+            const unsigned ggrid = (unsigned)std::min<int64_t>((g.R + 63) / 64, (int64_t)cus * kOuterWgs);
             if (int rc = launch_outer(g, ggrid, s)) return rc;
         }
         if (ovl) LDPC_HIP(hipEventRecord(ev_free[l & 1], s));  // this layer's set is free again
@@ -2098,14 +2068,14 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
                                    w.Mdb, w.dX, p->vgroup, p->cgroup, d_msg_var, d_llr, H, p->Gv, p->Gc, N, E, B, 1,
                                    w.dXp, w.hv, w.hc);
             LDPC_CHECK_LAUNCH("train_combine_sum_kernel");
-            v.mode = 0; v.g0 = Gw[0];
+            v.mode = 0; v.g0 = Gw.emb;
             if (int rc = launch_vecfinal(v, w.hv, w.hc, s)) return rc;
             if (l == 0) {  // dw_in from sum dc * llr, db_in from sum dc
                 v.mode = 1; v.g0 = d_grad_weights; v.g1 = d_grad_weights + H;
                 if (int rc = launch_vecfinal(v, w.hc, w.hv, s)) return rc;
             }
         } else {
-            v.mode = 0; v.g0 = Gw[0];
+            v.mode = 0; v.g0 = Gw.emb;
             if (int rc = launch_vec(v, w.hv, w.hc, s)) return rc;
             if (l == 0) {
                 v.mode = 1; v.g0 = d_grad_weights; v.g1 = d_grad_weights + H;
@@ -2148,11 +2118,10 @@ extern "C" int ldpc_gnn_layer_probs(const ldpc_gnn_plan *p, int hidden, int type
     float *msg_out = static_cast<float *>(d_work);
     int32_t *csr = reinterpret_cast<int32_t *>(msg_out + mo);
     if (int rc = gnn_build_var_csr(d_msg_var, E, N, csr, s)) return rc;
-    const float *WL[11];
-    t_layer(d_weights, H, T, L - 1, WL);
+    const auto WL = gnn_layer_weights(d_weights, H, T, L - 1);
     for (int l = 0; l < L - 1; ++l) {
         hipLaunchKernelGGL(train_msg_head_kernel, dim3((unsigned)((R * 16 + 255) / 256)), dim3(256), 0, s,
-                           d_saved + (int64_t)l * R * H, H, R, WL[9], WL[10], msg_out);
+                           d_saved + (int64_t)l * R * H, H, R, WL.wo, WL.bo, msg_out);
         LDPC_CHECK_LAUNCH("train_msg_head_kernel");
         if (int rc = gnn_output(msg_out, csr, d_llr, E, N, B, nullptr, d_layer_probs + (int64_t)l * B * N, s)) return rc;
     }

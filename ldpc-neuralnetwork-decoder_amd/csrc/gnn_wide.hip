@@ -504,13 +504,12 @@ __device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds) {
 
 // one workgroup per layer: both power-of-two weight scales, then every slice image of the layer
 template <int H>
-__global__ __launch_bounds__(1024) void gnn_wide_prep_kernel(const float *blob, int64_t layer_floats, int T,
-                                                              char *wimg, int *wexp) {
+__global__ __launch_bounds__(1024) void gnn_wide_prep_kernel(const float *blob, int T, char *wimg, int *wexp) {
     using F = WFused<H>;
     __shared__ uint32_t m1b, m2b;
     const int tid = threadIdx.x, l = blockIdx.x;
-    const float *w1v = blob + 2 * H + (int64_t)l * layer_floats + (int64_t)T * H;
-    const float *w2v = w1v + 2 * H * H + H, *w1c = w2v + H * H + H, *w2c = w1c + 2 * H * H + H;
+    const auto lw = gnn_layer_weights(blob, H, T, l);
+    const float *w1v = lw.w1v, *w2v = lw.w2v, *w1c = lw.w1c, *w2c = lw.w2c;
     if (tid == 0) { m1b = 0u; m2b = 0u; }
     __syncthreads();
     float m1 = 0.0f, m2 = 0.0f;
@@ -785,8 +784,6 @@ __global__ __launch_bounds__(WFused<H>::NTH, 1) void gnn_wide_mlp_kernel(WMlp A)
     }
 }
 
-int g_wcus = 0;
-
 template <int NT, int AH, bool F16>
 int go_wgemm(const WArgs &a, int nslices, dim3 grid, size_t lds, hipStream_t s) {
     LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gnn_wgemm_kernel<NT, AH, F16>),
@@ -803,11 +800,8 @@ int go_wgemm_nt(const WArgs &a, int nslices, dim3 grid, size_t lds, hipStream_t 
 }
 
 int launch_wgemm(WArgs a, bool f16, hipStream_t s) {
-    if (!g_wcus) {
-        int dev = 0;
-        LDPC_HIP(hipGetDevice(&dev));
-        LDPC_HIP(hipDeviceGetAttribute(&g_wcus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    int cus = 0;
+    if (int rc = gnn_num_cus(&cus)) return rc;
     if (a.R <= 0) return LDPC_OK;
     if (!f16) a.out_max = nullptr;
     // the widest output slice (4, 2 or 1 tiles of 32 units) whose split images fit the LDS
@@ -824,7 +818,7 @@ int launch_wgemm(WArgs a, bool f16, hipStream_t s) {
     const int nslices = a.H / a.NS;
     const int per_cu = std::max(1, std::min(2, (int)((160 * 1024) / lds)));
     // blocks per XCD: a multiple of the slice count, about per_cu workgroups per CU
-    const int per_x = std::max(nslices, (g_wcus / 8) * per_cu / nslices * nslices);
+    const int per_x = std::max(nslices, (cus / 8) * per_cu / nslices * nslices);
     if ((a.K / 16) % 2) return fail(LDPC_EUNSUPPORTED, "row GEMM reduction length must be a multiple of 32");
     const bool ah4 = (a.K / 16) % 4 == 0;
     const dim3 grid(8 * per_x);
@@ -836,6 +830,8 @@ int launch_wgemm(WArgs a, bool f16, hipStream_t s) {
 
 template <int H>
 int launch_wide_mlp(const WMlp &a, hipStream_t s) {
+    int cus = 0;
+    if (int rc = gnn_num_cus(&cus)) return rc;
     const size_t lds = wide_mlp_lds_bytes<H>(a.T);
     if (lds > 160 * 1024) return fail(LDPC_EUNSUPPORTED, "too many message types for the fused wide MLP's LDS image");
     const void *fn = a.x_in ? reinterpret_cast<const void *>(gnn_wide_mlp_kernel<H, false>)
@@ -843,7 +839,7 @@ int launch_wide_mlp(const WMlp &a, hipStream_t s) {
     LDPC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // one workgroup per CU, a multiple of the eight XCDs
     const int64_t tiles = (a.R + 31) / 32;
-    const int per_x = (int)std::max<int64_t>(1, std::min<int64_t>(g_wcus / 8, (tiles + 8 * WFused<H>::NW - 1) / (8 * WFused<H>::NW)));
+    const int per_x = (int)std::max<int64_t>(1, std::min<int64_t>(cus / 8, (tiles + 8 * WFused<H>::NW - 1) / (8 * WFused<H>::NW)));
     if (a.x_in)
         hipLaunchKernelGGL((gnn_wide_mlp_kernel<H, false>), dim3(8 * per_x), dim3(WFused<H>::NTH), lds, s, a);
     else
@@ -852,14 +848,11 @@ int launch_wide_mlp(const WMlp &a, hipStream_t s) {
     return LDPC_OK;
 }
 
-// LDPC_GNN_WIDE_GM_V=1 / 2 / 4: float4 per lane in the group means (A/B); default LDPC_WIDE_GM_V
-#ifndef LDPC_WIDE_GM_V
-#define LDPC_WIDE_GM_V 2
-#endif
+// LDPC_GNN_WIDE_GM_V=1 / 2 / 4: float4 per lane in the group means (A/B); default 2
 int gm_v() {
     static const int v = [] {
         const char *e = std::getenv("LDPC_GNN_WIDE_GM_V");
-        const int x = e ? std::atoi(e) : LDPC_WIDE_GM_V;
+        const int x = e ? std::atoi(e) : 2;
         return x == 1 || x == 4 ? x : 2;
     }();
     return v;
@@ -905,25 +898,26 @@ bool gnn_wide_fused_fits(int H, int T) {
 }
 
 template <int H>
-void go_prep(int layers, const float *blob, int64_t layer_floats, int T, char *wimg, int *wexp, hipStream_t s) {
-    hipLaunchKernelGGL(gnn_wide_prep_kernel<H>, dim3(layers), dim3(1024), 0, s, blob, layer_floats, T, wimg, wexp);
+void go_prep(int layers, const float *blob, int T, char *wimg, int *wexp, hipStream_t s) {
+    hipLaunchKernelGGL(gnn_wide_prep_kernel<H>, dim3(layers), dim3(1024), 0, s, blob, T, wimg, wexp);
 }
 
-int gnn_wide_memb(const ldpc_gnn_plan *p, int H, int layers, const float *emb0, int64_t layer_stride,
-                  const int32_t *msg_type, float *memb, hipStream_t s) {
+int gnn_wide_memb(const ldpc_gnn_plan *p, int H, int T, int layers, const float *blob, const int32_t *msg_type,
+                  float *memb, hipStream_t s) {
     const int64_t n = (int64_t)layers * (p->Gv + p->Gc) * H;
-    hipLaunchKernelGGL(gnn_wide_memb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, emb0, layer_stride, H,
+    hipLaunchKernelGGL(gnn_wide_memb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                       gnn_layer_weights(blob, H, T, 0).emb, gnn_layer_floats(H, T), H,
                        msg_type, p->vg_ptr, p->vg_mem, p->inv_v, p->cg_ptr, p->cg_mem, p->inv_c, p->Gv, p->Gc, layers, memb);
     LDPC_CHECK_LAUNCH("gnn_wide_memb_kernel");
     return LDPC_OK;
 }
 
-int gnn_wide_prep(int H, int layers, const float *blob, int64_t layer_floats, int T, char *wimg, int *wexp, hipStream_t s) {
+int gnn_wide_prep(int H, int layers, const float *blob, int T, char *wimg, int *wexp, hipStream_t s) {
     switch (H) {
-        case 96: go_prep<96>(layers, blob, layer_floats, T, wimg, wexp, s); break;
-        case 128: go_prep<128>(layers, blob, layer_floats, T, wimg, wexp, s); break;
-        case 160: go_prep<160>(layers, blob, layer_floats, T, wimg, wexp, s); break;
-        case 192: go_prep<192>(layers, blob, layer_floats, T, wimg, wexp, s); break;
+        case 96: go_prep<96>(layers, blob, T, wimg, wexp, s); break;
+        case 128: go_prep<128>(layers, blob, T, wimg, wexp, s); break;
+        case 160: go_prep<160>(layers, blob, T, wimg, wexp, s); break;
+        case 192: go_prep<192>(layers, blob, T, wimg, wexp, s); break;
         default: return fail(LDPC_EINVAL, "fused wide MLP: H must be 96, 128, 160 or 192");
     }
     LDPC_CHECK_LAUNCH("gnn_wide_prep_kernel");
@@ -937,7 +931,7 @@ int gnn_wide_layer(const GnnWideLayer &L, hipStream_t s) {
     {
         WGm g{};
         g.x = L.x_in;
-        g.llr = L.llr; g.w_in = L.w_in; g.b_in = L.b_in; g.emb = L.emb;
+        g.llr = L.llr; g.w_in = L.w_in; g.b_in = L.b_in; g.emb = L.w.emb;
         g.msg_type = L.msg_type; g.msg_var = L.msg_var;
         g.meta = L.plan->gt_meta; g.grp = L.plan->gt_grp; g.mem = L.plan->gt_mem; g.n_tiles = L.plan->n_gtiles;
         g.inv_v = L.plan->inv_v; g.inv_c = L.plan->inv_c;
@@ -964,7 +958,7 @@ int gnn_wide_layer(const GnnWideLayer &L, hipStream_t s) {
     }
     WArgs base{};
     base.H = H;
-    base.emb = L.emb; base.msg_type = L.msg_type; base.msg_var = L.msg_var;
+    base.emb = L.w.emb; base.msg_type = L.msg_type; base.msg_var = L.msg_var;
     base.llr = L.llr; base.w_in = L.w_in; base.b_in = L.b_in; base.N = L.N; base.T = L.T; base.E = L.E;
     // projections P_s = W1_s,right g + b1_s
     for (int side = 0; side < 2; ++side) {
@@ -974,27 +968,22 @@ int gnn_wide_layer(const GnnWideLayer &L, hipStream_t s) {
         a.R = L.B * (side ? L.plan->Gc : L.plan->Gv);
         a.in = side ? L.Mc : L.Mv;
         a.in_stride = H;
-        a.w_a = side ? L.w1c : L.w1v;
+        a.w_a = side ? L.w.w1c : L.w.w1v;
         a.ld = 2 * H;
         a.col0 = H;
-        a.init_a = side ? L.b1c : L.b1v;
+        a.init_a = side ? L.w.b1c : L.w.b1v;
         a.out = side ? L.Pc : L.Pv;
         a.out_stride = H;
         a.in_max = side ? L.gmax_c : L.gmax_v;
         if (int rc = launch_wgemm(a, L.f16, s)) return rc;
     }
     if (L.wimg) {  // H = 96 / 128: GEMM1 -> GEMM2 (-> head) fused per tile
-        if (!g_wcus) {
-            int dev = 0;
-            LDPC_HIP(hipGetDevice(&dev));
-            LDPC_HIP(hipDeviceGetAttribute(&g_wcus, hipDeviceAttributeMultiprocessorCount, dev));
-        }
         WMlp a{};
         a.wimg = L.wimg; a.wexp = L.wexp;
-        a.x_in = L.x_in; a.llr = L.llr; a.w_in = L.w_in; a.b_in = L.b_in; a.emb = L.emb;
+        a.x_in = L.x_in; a.llr = L.llr; a.w_in = L.w_in; a.b_in = L.b_in; a.emb = L.w.emb;
         a.msg_type = L.msg_type; a.msg_var = L.msg_var; a.vgroup = L.plan->vgroup; a.cgroup = L.plan->cgroup;
         a.Pv = L.Pv; a.Pc = L.Pc;
-        a.b2v = L.b2v; a.b2c = L.b2c; a.wo = L.wo; a.bo = L.bo;
+        a.b2v = L.w.b2v; a.b2c = L.w.b2c; a.wo = L.w.wo; a.bo = L.w.bo;
         a.y = L.y; a.msg_out = L.msg_out;
         a.residual = L.residual; a.N = L.N; a.T = L.T; a.Gv = L.plan->Gv; a.Gc = L.plan->Gc;
         a.E = L.E; a.R = BE;
@@ -1014,7 +1003,7 @@ int gnn_wide_layer(const GnnWideLayer &L, hipStream_t s) {
         a.R = BE;
         a.in = L.x_in;
         a.in_stride = H;
-        a.w_a = side ? L.w1c : L.w1v;
+        a.w_a = side ? L.w.w1c : L.w.w1v;
         a.ld = 2 * H;
         a.col0 = 0;
         a.init_a = side ? L.Pc : L.Pv;
@@ -1034,10 +1023,10 @@ int gnn_wide_layer(const GnnWideLayer &L, hipStream_t s) {
         a.R = BE;
         a.in = L.hbuf;
         a.in_stride = 2 * H;
-        a.w_a = L.w2v;
-        a.w_b = L.w2c;
-        a.init_a = L.b2v;
-        a.init_b = L.b2c;
+        a.w_a = L.w.w2v;
+        a.w_b = L.w.w2c;
+        a.init_a = L.w.b2v;
+        a.init_b = L.w.b2c;
         a.resid = L.residual ? L.x_in : nullptr;
         a.out = L.y;
         a.out_stride = H;
@@ -1048,7 +1037,7 @@ int gnn_wide_layer(const GnnWideLayer &L, hipStream_t s) {
     }
     if (L.msg_out) {
         hipLaunchKernelGGL(gnn_wide_head_kernel, dim3((unsigned)((BE * 16 + 255) / 256)), dim3(256), 0, s, L.y, H, BE,
-                           L.wo, L.bo, L.msg_out);
+                           L.w.wo, L.w.bo, L.msg_out);
         LDPC_CHECK_LAUNCH("gnn_wide_head_kernel");
     }
     return LDPC_OK;
