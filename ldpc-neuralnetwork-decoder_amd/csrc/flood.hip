@@ -9,7 +9,8 @@
 // lives in LDS for the whole decode (layout: graph.hpp).  HBM sees the LLRs once (plus L2 re-reads
 // of degree-1 columns) and the decisions once.  Per iteration:
 //   check phase  each wave takes whole block-rows (LPT schedule); a lane owns check r*Z+k of
-//                frame f, keeps the row's <= 24 messages in registers, writes c2v in place
+//                frame f, keeps the row's messages in registers (re-reads them past degree 12),
+//                writes c2v in place
 //   var phase    each wave takes whole columns; a lane owns variable c*Z+t, reads its dv c2v
 //                (rotated slot index), writes v2c in place as the reference's ordered sums
 //   [ES]         decisions as 64-bit ballots per column in LDS, syndrome per block-row
@@ -18,13 +19,13 @@
 // v2c_i = (((llr + c_0) + c_1) ...) over i' != i in ascending check order; we compute it as the
 // prefix P_i followed by the same tail adds, i.e. the identical operation sequence.  Min-sum's
 // sign/min is order-free.  BP's exclusive product is prefix-then-tail as well; tanh/atanh are
-// float32 approximations of a few ulp (tanh_half / two_atanh below; the reference uses torch-CPU
-// SLEEF float versions; neither is correctly rounded, so BP parity is "within float32
+// float32 approximations of a few ulp (tanh_half / two_atanh in flood_dev.hpp; the reference uses
+// torch-CPU SLEEF float versions; neither is correctly rounded, so BP parity is "within float32
 // tolerance", not bitwise).
 // Compile with -ffp-contract=off: no a*b+c may fuse on this path.
 // Translation units: flood_dev.hpp (device code shared by all), flood_fixed_ms.hip / flood_fixed_bp.hip
-// (compile-time schedules), flood_stream.hip (streaming decoders), flood_layered.hip (layered min-sum),
-// and this file (table-driven kernel, early-stop passes, host dispatch, the C ABI).
+// (compile-time schedules: flood_fixed.hpp), flood_stream.hip (streaming decoders), flood_layered.hip
+// (layered min-sum), and this file (table-driven kernel, early-stop passes, host dispatch, the C ABI).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(256) void bp_math_kernel(const float *__restrict__ 
     if (at) at[i] = two_atanh(v);
 }
 
-// Second launch behind a bail-out instance of flood_fixed_kernel (flood_dev.hpp Body::kBail): the
+// Second launch behind a bail-out instance of flood_fixed_kernel (flood_drive, Body::kBail): the
 // groups on its redo list are decoded again from their LLRs by the table-driven update, which is
 // bit-identical and exact for every value, and get their bits, iteration counts and counter rows
 // here.  A fixed small grid strides over the list; with an empty list (no non-finite value in the
@@ -236,40 +237,32 @@ bool has_redo(const ldpc_graph *g, int algo, int es) {
 
 // redo (has_redo decodes, NULL without a workspace): the redo list of FloodWs
 template <int ALGO, int ES>
-int launch_flood(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int out_dtype,
-                 void *bits, const Outs &O, const EsWs &W, hipStream_t s, uint32_t *redo = nullptr) {
+int launch_flood(const FloodCall &c, const Outs &O, const EsWs &W, uint32_t *redo = nullptr) {
+    const ldpc_graph *g = c.g;
     const size_t lds = flood_lds_bytes(g, ES);
-    const int64_t nwg = (B + g->FG - 1) / g->FG;
+    const int64_t nwg = (c.B + g->FG - 1) / g->FG;
+    const dim3 block(64 * g->ft.W);
     if (g->fixed_id != 0) {  // compile-time schedules: their own translation units
-        const dim3 grid((unsigned)nwg), block(64 * g->ft.W);
-        if constexpr (ALGO == LDPC_ALGO_MINSUM && (ES == LDPC_ES_OFF || ES == LDPC_ES_FRAME)) {
-            if (redo) {
-                LDPC_HIP(hipMemsetAsync(redo, 0, sizeof(uint32_t), s));
-                int rc = launch_fixed_minsum(g->fixed_id, ES, grid, block, lds, s, g->ft, llr, B, max_iter, alpha,
-                                             out_dtype, bits, O, W, redo);
-                if (rc != LDPC_OK) return rc;
-                auto again = flood_redo_kernel<ES>;
-                LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(again),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                Outs Or = O;
-                Or.timeline = nullptr;
-                hipLaunchKernelGGL(again, dim3((unsigned)std::min<int64_t>(nwg, kRedoGrid)), block, lds, s, g->ft, llr,
-                                   B, max_iter, alpha, out_dtype, bits, Or, (const uint32_t *)redo);
-                LDPC_CHECK_LAUNCH("flood_redo_kernel");
-                return LDPC_OK;
-            }
+        if (redo) LDPC_HIP(hipMemsetAsync(redo, 0, sizeof(uint32_t), c.s));
+        const int rc = launch_fixed<ALGO>(c, ES, lds, O, W, redo);
+        if (rc != LDPC_OK || !redo) return rc;
+        if constexpr (ES == LDPC_ES_OFF || ES == LDPC_ES_FRAME) {
+            auto again = flood_redo_kernel<ES>;
+            LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(again),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            Outs Or = O;
+            Or.timeline = nullptr;
+            hipLaunchKernelGGL(again, dim3((unsigned)std::min<int64_t>(nwg, kRedoGrid)), block, lds, c.s, g->ft, c.llr,
+                               c.B, c.max_iter, c.alpha, c.out_dtype, c.bits, Or, (const uint32_t *)redo);
+            LDPC_CHECK_LAUNCH("flood_redo_kernel");
         }
-        return ALGO == LDPC_ALGO_MINSUM
-                   ? launch_fixed_minsum(g->fixed_id, ES, grid, block, lds, s, g->ft, llr, B, max_iter, alpha,
-                                         out_dtype, bits, O, W, nullptr)
-                   : launch_fixed_bp(g->fixed_id, ES, grid, block, lds, s, g->ft, llr, B, max_iter, alpha,
-                                     out_dtype, bits, O, W);
+        return LDPC_OK;
     }
     auto kern = flood_kernel<ALGO, ES>;
     LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * g->ft.W), lds, s, g->ft, llr, B, max_iter, alpha,
-                       out_dtype, bits, O, W);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), block, lds, c.s, g->ft, c.llr, c.B, c.max_iter, c.alpha,
+                       c.out_dtype, c.bits, O, W);
     LDPC_CHECK_LAUNCH("flood_kernel");
     return LDPC_OK;
 }
@@ -283,11 +276,15 @@ int reduce_rows(const ldpc_graph *g, int64_t B, const uint32_t *partials, uint64
 }
 
 template <int ALGO>
-int run_flood(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int es, int out_dtype,
-              void *bits, int32_t *iters_out, uint64_t *counters, int32_t *batch_iters, void *work, hipStream_t s) {
-    const FloodWs ws = flood_ws(g, B, max_iter, es, work);
-    const bool want = counters || batch_iters;
-    const Outs O{iters_out, want ? ws.partials : nullptr};
+int run_flood(const FloodCall &c) {
+    const ldpc_graph *g = c.g;
+    const int64_t B = c.B;
+    const int max_iter = c.max_iter, es = c.es;
+    hipStream_t s = c.s;
+    const FloodWs ws = flood_ws(g, B, max_iter, es, c.work);
+    const bool want = c.counters || c.batch_iters;
+    const Outs O{c.iters, want ? ws.partials : nullptr};
+    uint32_t *redo = has_redo(g, ALGO, es) ? ws.redo : nullptr;
     if (es == LDPC_ES_OFF) {
 #ifdef LDPC_TIMELINE
         // timeline build: stamps of the first kTlWgs workgroups, dumped after the decode to
@@ -298,7 +295,7 @@ int run_flood(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, fl
         LDPC_HIP(hipMemsetAsync(tl, 0, tl_n * 8, s));
         Outs Ot = O;
         Ot.timeline = tl;
-        int rc = launch_flood<ALGO, LDPC_ES_OFF>(g, llr, B, max_iter, alpha, out_dtype, bits, Ot, EsWs{}, s, ws.redo);
+        int rc = launch_flood<ALGO, LDPC_ES_OFF>(c, Ot, EsWs{}, redo);
         if (const char *path = std::getenv("LDPC_TIMELINE_OUT")) {
             std::vector<uint64_t> h(tl_n);
             LDPC_HIP(hipStreamSynchronize(s));
@@ -311,42 +308,42 @@ int run_flood(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, fl
             }
         }
 #else
-        int rc = launch_flood<ALGO, LDPC_ES_OFF>(g, llr, B, max_iter, alpha, out_dtype, bits, O, EsWs{}, s, ws.redo);
+        int rc = launch_flood<ALGO, LDPC_ES_OFF>(c, O, EsWs{}, redo);
 #endif
         // ES off: every frame ran max_iter (batch_iters was set before the launch)
-        return rc != LDPC_OK ? rc : reduce_rows(g, B, ws.partials, counters, nullptr, nullptr, s);
+        return rc != LDPC_OK ? rc : reduce_rows(g, B, ws.partials, c.counters, nullptr, nullptr, s);
     }
     if (es == LDPC_ES_FRAME) {
-        int rc = launch_flood<ALGO, LDPC_ES_FRAME>(g, llr, B, max_iter, alpha, out_dtype, bits, O, EsWs{}, s, ws.redo);
-        return rc != LDPC_OK ? rc : reduce_rows(g, B, ws.partials, counters, batch_iters, nullptr, s);
+        int rc = launch_flood<ALGO, LDPC_ES_FRAME>(c, O, EsWs{}, redo);
+        return rc != LDPC_OK ? rc : reduce_rows(g, B, ws.partials, c.counters, c.batch_iters, nullptr, s);
     }
     const EsWs &W = ws.es;
     hipLaunchKernelGGL(es_init_kernel, dim3(1), dim3(64), 0, s, W.ctl, W.staged, ws.all);
     LDPC_CHECK_LAUNCH("es_init_kernel");
     LDPC_HIP(hipMemsetAsync(W.valid, 0, (size_t)B * W.nvw * 4, s));
-    int rc = launch_flood<ALGO, ES_P1>(g, llr, B, max_iter, alpha, out_dtype, bits, Outs{}, W, s);
+    int rc = launch_flood<ALGO, ES_P1>(c, Outs{}, W);
     if (rc != LDPC_OK) return rc;
     // P2 always writes its counter rows: they become `staged`, applied by es_finalize_kernel
-    rc = launch_flood<ALGO, ES_P2>(g, llr, B, max_iter, alpha, out_dtype, bits, Outs{iters_out, ws.partials}, W, s);
+    rc = launch_flood<ALGO, ES_P2>(c, Outs{c.iters, ws.partials}, W);
     if (rc != LDPC_OK) return rc;
     rc = reduce_rows(g, B, ws.partials, W.staged, nullptr, nullptr, s);
     if (rc != LDPC_OK) return rc;
     // LDPC_FLOOD_ES_FALLBACK=1 forces the exhaustive pass (tests: both paths must agree)
     const char *ff = std::getenv("LDPC_FLOOD_ES_FALLBACK");
-    hipLaunchKernelGGL(es_finalize_kernel, dim3(1), dim3(1), 0, s, W.ctl, max_iter, W.staged, counters,
-                       batch_iters, (ff && std::atoi(ff) != 0) ? 1 : 0);
+    hipLaunchKernelGGL(es_finalize_kernel, dim3(1), dim3(1), 0, s, W.ctl, max_iter, W.staged, c.counters,
+                       c.batch_iters, (ff && std::atoi(ff) != 0) ? 1 : 0);
     LDPC_CHECK_LAUNCH("es_finalize_kernel");
     // fallback (runs only when es_finalize_kernel found a frame invalid at T)
-    rc = launch_flood<ALGO, LDPC_ES_BATCH>(g, llr, B, max_iter, alpha, out_dtype, bits, Outs{}, W, s);
+    rc = launch_flood<ALGO, LDPC_ES_BATCH>(c, Outs{}, W);
     if (rc != LDPC_OK) return rc;
     hipLaunchKernelGGL(batch_and_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, W.valid, B, W.nvw, ws.all,
                        W.ctl);
     LDPC_CHECK_LAUNCH("batch_and_kernel");
     const int64_t nwg = (B + g->FG - 1) / g->FG;
     hipLaunchKernelGGL(batch_emit_kernel, dim3((unsigned)nwg), dim3(64 * g->ft.W), 0, s, g->ft, W.words, ws.all,
-                       max_iter, W.nvw, B, out_dtype, bits, iters_out, want ? ws.partials : nullptr, W.ctl);
+                       max_iter, W.nvw, B, c.out_dtype, c.bits, c.iters, want ? ws.partials : nullptr, W.ctl);
     LDPC_CHECK_LAUNCH("batch_emit_kernel");
-    return reduce_rows(g, B, ws.partials, counters, batch_iters, W.ctl + 2, s);
+    return reduce_rows(g, B, ws.partials, c.counters, c.batch_iters, W.ctl + 2, s);
 }
 }  // namespace
 
@@ -404,20 +401,11 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
         hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(1), 0, s, d_batch_iters, max_iter);
         LDPC_CHECK_LAUNCH("fill");
     }
-    if (algo == LDPC_ALGO_LAYERED_MINSUM)
-        return run_layered(g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits, d_iters, d_counters,
-                           d_batch_iters, d_work, s);
-    if (streaming)
-        return algo == LDPC_ALGO_MINSUM
-                   ? run_stream_decode(LDPC_ALGO_MINSUM, g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits,
-                                       d_iters, d_counters, d_batch_iters, d_work, s)
-                   : run_stream_decode(LDPC_ALGO_BP, g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits,
-                                       d_iters, d_counters, d_batch_iters, d_work, s);
-    return algo == LDPC_ALGO_MINSUM
-               ? run_flood<LDPC_ALGO_MINSUM>(g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits, d_iters,
-                                             d_counters, d_batch_iters, d_work, s)
-               : run_flood<LDPC_ALGO_BP>(g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits, d_iters,
-                                         d_counters, d_batch_iters, d_work, s);
+    const FloodCall c{g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits, d_iters, d_counters, d_batch_iters,
+                      d_work, s};
+    if (algo == LDPC_ALGO_LAYERED_MINSUM) return run_layered(c);
+    if (streaming) return run_stream_decode(algo, c);
+    return algo == LDPC_ALGO_MINSUM ? run_flood<LDPC_ALGO_MINSUM>(c) : run_flood<LDPC_ALGO_BP>(c);
 }
 
 extern "C" int ldpc_flood_redo_count(const ldpc_graph *g, int algo, int64_t B, int max_iter, int early_stop,

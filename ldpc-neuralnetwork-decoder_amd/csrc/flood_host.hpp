@@ -14,30 +14,42 @@ inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 int reduce_counter_rows(const uint32_t *partials, int64_t nwg, uint64_t *counters, int32_t *batch_iters,
                         const int32_t *gate, hipStream_t s);
 
-// flood_fixed_ms.hip / flood_fixed_bp.hip: flood_fixed_kernel<code, ALGO, es> for fixed_id 1 (BG2 Z=4)
-// or 2 (BG2 Z=32), es one of LDPC_ES_OFF / LDPC_ES_FRAME / LDPC_ES_BATCH / ES_P1 / ES_P2.
-// redo (min-sum, LDPC_ES_OFF / LDPC_ES_FRAME only; may be NULL): [0] a count the caller has zeroed,
+// One decode as ldpc_flood_decode has checked it: the arguments every flooding / layered / streaming
+// path takes (device pointers; work may be NULL where the path needs none).
+struct FloodCall {
+    const ldpc_graph *g;
+    const float *llr;
+    int64_t B;
+    int max_iter;
+    float alpha;
+    int es;  // the caller's early_stop: LDPC_ES_OFF / LDPC_ES_BATCH / LDPC_ES_FRAME
+    int out_dtype;
+    void *bits;
+    int32_t *iters;
+    uint64_t *counters;
+    int32_t *batch_iters;
+    void *work;
+    hipStream_t s;
+};
+
+// flood_fixed.hpp, instantiated by flood_fixed_ms.hip (min-sum) and flood_fixed_bp.hip (BP):
+// flood_fixed_kernel<code, ALGO, es> for fixed_id 1 (BG2 Z=4) or 2 (BG2 Z=32), es one of LDPC_ES_OFF /
+// LDPC_ES_FRAME / LDPC_ES_BATCH / ES_P1 / ES_P2 (the pass to launch, not c.es), lds its dynamic LDS.
+// redo (min-sum, LDPC_ES_OFF / LDPC_ES_FRAME only; NULL otherwise): [0] a count the caller has zeroed,
 // [1 ..] room for one entry per workgroup.  With it the kernel holds the fast check update only: a
 // workgroup that meets a non-finite value appends its index and writes no counter row, and the
-// caller decodes the listed groups again with the table-driven kernel (flood.hip run_flood).
-int launch_fixed_minsum(int fixed_id, int es, dim3 grid, dim3 block, size_t lds, hipStream_t s, const FloodTables &T,
-                        const float *llr, int64_t B, int max_iter, float alpha, int out_dtype, void *bits,
-                        const Outs &O, const EsWs &W, uint32_t *redo);
-int launch_fixed_bp(int fixed_id, int es, dim3 grid, dim3 block, size_t lds, hipStream_t s, const FloodTables &T,
-                    const float *llr, int64_t B, int max_iter, float alpha, int out_dtype, void *bits, const Outs &O,
-                    const EsWs &W);
+// caller decodes the listed groups again with the table-driven kernel (flood.hip launch_flood).
+template <int ALGO>
+int launch_fixed(const FloodCall &c, int es, size_t lds, const Outs &O, const EsWs &W, uint32_t *redo);
 
-// flood_layered.hip: layered min-sum (LDS-resident only; es is LDPC_ES_OFF or LDPC_ES_FRAME).  work holds the
-// counter rows, one per FG frames: the head of the flooding workspace of the same arguments.
+// flood_layered.hip: layered min-sum (LDS-resident only; c.es is LDPC_ES_OFF or LDPC_ES_FRAME).  c.work holds
+// the counter rows, one per FG frames: the head of the flooding workspace of the same arguments.
 size_t layered_lds_bytes(const ldpc_graph *g, int es);
-int run_layered(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int es, int out_dtype,
-                void *bits, int32_t *iters_out, uint64_t *counters, int32_t *batch_iters, void *work, hipStream_t s);
+int run_layered(const FloodCall &c);
 
 // flood_stream.hip: the streaming decoders (messages in HBM, any graph)
 int64_t stream_ws_bytes(const ldpc_graph *g, int64_t B, int max_iter);
-int run_stream_decode(int algo, const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int es,
-                      int out_dtype, void *bits, int32_t *iters_out, uint64_t *counters, int32_t *batch_iters,
-                      void *work, hipStream_t s);
+int run_stream_decode(int algo, const FloodCall &c);
 int64_t custom_ws_bytes(const ldpc_graph *g, int64_t B);
 int run_custom_minsum(const ldpc_graph *g, const float *llr, int64_t B, int iterations, float *probs, void *work,
                       hipStream_t s);

@@ -34,8 +34,8 @@
 // layer boundary.  No other wave ever touches these bytes.
 // Compile with -ffp-contract=off: no a*b+c may fuse on this path.
 #include <string>
-
 #include "flood_host.hpp"
+#include "gen/fixed_codes.hpp"
 
 namespace ldpc {
 namespace {
@@ -486,32 +486,32 @@ size_t layered_lds_bytes(const ldpc_graph *g, int es) {
     return b;
 }
 
-int run_layered(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int es, int out_dtype,
-                void *bits, int32_t *iters_out, uint64_t *counters, int32_t *batch_iters, void *work,
-                hipStream_t s) {
-    const int64_t nwg = (B + g->FG - 1) / g->FG;
-    const bool want = counters || (batch_iters && es == LDPC_ES_FRAME);
-    const Outs O{iters_out, want ? static_cast<uint32_t *>(work) : nullptr, nullptr};
+int run_layered(const FloodCall &c) {
+    const ldpc_graph *g = c.g;
+    const int es = c.es;
+    const int64_t nwg = (c.B + g->FG - 1) / g->FG;
+    const bool want = c.counters || (c.batch_iters && es == LDPC_ES_FRAME);
+    const Outs O{c.iters, want ? static_cast<uint32_t *>(c.work) : nullptr, nullptr};
     if (g->fixed_id == 2) {  // compile-time schedule: BG2 Z=32
         using FB = LayFixedBody<fixed::BG2_Z32>;
         const size_t lds = (size_t)FB::NCORE * 256 + (es != LDPC_ES_OFF ? (size_t)g->Nb * sizeof(uint64_t) : 0);
         auto kern = es == LDPC_ES_OFF ? layered_fixed_kernel<fixed::BG2_Z32, LDPC_ES_OFF>
                                       : layered_fixed_kernel<fixed::BG2_Z32, LDPC_ES_FRAME>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64), lds, s, g->ft, llr, B, max_iter, alpha, out_dtype, bits,
-                           O);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64), lds, c.s, g->ft, c.llr, c.B, c.max_iter, c.alpha,
+                           c.out_dtype, c.bits, O);
         LDPC_CHECK_LAUNCH("layered_fixed_kernel");
     } else {
         const size_t lds = layered_lds_bytes(g, es);
         auto kern = es == LDPC_ES_OFF ? layered_kernel<LDPC_ES_OFF> : layered_kernel<LDPC_ES_FRAME>;
         LDPC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64), lds, s, g->ft, g->lt, llr, B, max_iter, alpha,
-                           out_dtype, bits, O);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64), lds, c.s, g->ft, g->lt, c.llr, c.B, c.max_iter, c.alpha,
+                           c.out_dtype, c.bits, O);
         LDPC_CHECK_LAUNCH("layered_kernel");
     }
     if (!want) return LDPC_OK;
     // ES off: every frame ran max_iter (batch_iters was set before the launch)
-    return reduce_counter_rows(O.partials, nwg, counters, es == LDPC_ES_FRAME ? batch_iters : nullptr, nullptr, s);
+    return reduce_counter_rows(O.partials, nwg, c.counters, es == LDPC_ES_FRAME ? c.batch_iters : nullptr, nullptr, c.s);
 }
 
 }  // namespace ldpc

@@ -415,16 +415,19 @@ void launch_custom_var(const ldpc_graph *g, const StreamArgs &S, int64_t B, int 
 }
 
 template <int ALGO>
-int run_stream(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int es, int out_dtype,
-               void *bits, int32_t *iters_out, uint64_t *counters, int32_t *batch_iters, void *work, hipStream_t s) {
-    const StreamWs w = stream_ws(g, B, max_iter, work);
+int run_stream(const FloodCall &c) {
+    const ldpc_graph *g = c.g;
+    const int64_t B = c.B;
+    const int max_iter = c.max_iter, es = c.es;
+    hipStream_t s = c.s;
+    const StreamWs w = stream_ws(g, B, max_iter, c.work);
     StreamArgs S{g->chk_ptr, g->ev, g->var_ptr, g->var_edge, g->M, g->N, g->E, B, w.msg, w.llrT, w.bitsT, w.done,
-                 w.iters, w.ctl, w.invalid, alpha, es, g->ext_var};
+                 w.iters, w.ctl, w.invalid, c.alpha, es, g->ext_var};
     LDPC_HIP(hipMemsetAsync(w.done, 0, (size_t)B, s));
     LDPC_HIP(hipMemsetAsync(w.ctl, 0, 64, s));
     LDPC_HIP(hipMemsetAsync(w.invalid, 0, (size_t)max_iter * 4, s));
     const dim3 tgrid((unsigned)((B + 63) / 64), (unsigned)((g->N + 63) / 64));
-    hipLaunchKernelGGL(stream_transpose_llr_kernel, tgrid, dim3(256), 0, s, llr, B, g->N, w.llrT);
+    hipLaunchKernelGGL(stream_transpose_llr_kernel, tgrid, dim3(256), 0, s, c.llr, B, g->N, w.llrT);
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     for (int it = 0; it < max_iter; ++it) {
         if (it == 0)  // v2c = LLR (traditional_decoders.py:199-202) read in place of an init pass
@@ -438,13 +441,13 @@ int run_stream(const ldpc_graph *g, const float *llr, int64_t B, int max_iter, f
         }
         LDPC_CHECK_LAUNCH("stream iteration");
     }
-    const bool want = counters || batch_iters;
-    hipLaunchKernelGGL(stream_emit_kernel, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, S, max_iter, out_dtype,
-                       bits, iters_out, want ? w.partials : nullptr);
+    const bool want = c.counters || c.batch_iters;
+    hipLaunchKernelGGL(stream_emit_kernel, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, S, max_iter, c.out_dtype,
+                       c.bits, c.iters, want ? w.partials : nullptr);
     LDPC_CHECK_LAUNCH("stream emit");
     if (!want) return LDPC_OK;
     // batch_iters: ES off was set before the launch; otherwise the largest per-frame count
-    return reduce_counter_rows(w.partials, (B + 63) / 64, counters, es == LDPC_ES_OFF ? nullptr : batch_iters,
+    return reduce_counter_rows(w.partials, (B + 63) / 64, c.counters, es == LDPC_ES_OFF ? nullptr : c.batch_iters,
                                nullptr, s);
 }
 
@@ -490,14 +493,8 @@ int run_custom_minsum_(const ldpc_graph *g, const float *llr, int64_t B, int ite
 
 int64_t stream_ws_bytes(const ldpc_graph *g, int64_t B, int max_iter) { return stream_ws(g, B, max_iter, nullptr).bytes; }
 
-int run_stream_decode(int algo, const ldpc_graph *g, const float *llr, int64_t B, int max_iter, float alpha, int es,
-                      int out_dtype, void *bits, int32_t *iters_out, uint64_t *counters, int32_t *batch_iters,
-                      void *work, hipStream_t s) {
-    return algo == LDPC_ALGO_MINSUM
-               ? run_stream<LDPC_ALGO_MINSUM>(g, llr, B, max_iter, alpha, es, out_dtype, bits, iters_out, counters,
-                                              batch_iters, work, s)
-               : run_stream<LDPC_ALGO_BP>(g, llr, B, max_iter, alpha, es, out_dtype, bits, iters_out, counters,
-                                          batch_iters, work, s);
+int run_stream_decode(int algo, const FloodCall &c) {
+    return algo == LDPC_ALGO_MINSUM ? run_stream<LDPC_ALGO_MINSUM>(c) : run_stream<LDPC_ALGO_BP>(c);
 }
 
 int64_t custom_ws_bytes(const ldpc_graph *g, int64_t B) { return custom_ws_bytes_(g, B); }

@@ -20,12 +20,12 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CODES = [("BG2_Z4", os.path.join(ROOT, "codes", "NR_2_0_4.txt"), 4),
          ("BG2_Z32", os.path.join(ROOT, "codes", "NR_2_0_32.txt"), 32)]
 W = 4
-DIRECT_DC = 6  # the default of LDPC_DIRECT_DC in csrc/flood_dev.hpp
-# Register edges (RE_* arrays, LDPC_REG_EDGES in csrc/flood_dev.hpp): at most this many messages
+DIRECT_DC = 6  # the default of LDPC_DIRECT_DC in csrc/flood_fixed.hpp
+# Register edges (RE_* arrays, reg_edges() in csrc/flood_fixed.hpp): at most this many messages
 # per wave stay in VGPRs.  Above what the search finds for either code (BG2 Z=32: 11 per wave, 44;
 # BG2 Z=4: 15 / 14 / 14 / 15, 58), so every eligible edge is taken; a larger cap finds no more (at
 # Z=4 it only spreads the same 58 less evenly).  The kernel instances that cannot afford them all
-# keep the first LDPC_SLOW_REG_EDGES of a wave's (csrc/flood_dev.hpp FxPlan).
+# keep the first LDPC_SLOW_REG_EDGES of a wave's (csrc/flood_fixed.hpp FxPlan).
 REG_EDGE_CAP = 16
 # modelled LDS cycles a register edge saves: the check phase's per-edge term of the row costs, and
 # the read and the write of var_task_cost
@@ -111,11 +111,11 @@ def reg_edge_schedule(blocks, z, mb, dv, row_ptr, rcost, sched, cap):
     Returns (rho, rows per wave, register edges per wave as block indices in row order)."""
     colwave = {}
     for w, p in enumerate(sched):
-        for a, b, _, _ in p:
+        for a, b in p:
             colwave[a] = w
             if b >= 0:
                 colwave[b] = w
-    vbase = [sum(var_task_cost(dv[a], dv[b] if b >= 0 else 0, lo, hi) for a, b, lo, hi in p) for p in sched]
+    vbase = [sum(var_task_cost(dv[a], dv[b] if b >= 0 else 0) for a, b in p) for p in sched]
     edges = [list(range(row_ptr[r], row_ptr[r + 1])) for r in range(mb)]
     slot_edges = [[i for i in edges[r] if dv[blocks[i][1]] >= 2] for r in range(mb)]
     rhos = [sorted({0} | {(-blocks[i][2]) % z for i in slot_edges[r]}) for r in range(mb)]
@@ -247,8 +247,7 @@ def gen(name, base, z, reg_edges=True, cap=None, report=None):
              4.1 * n_min_ops(dc[r]) + 2.2 * (dc[r] // 2) + 10.4 * nslot[r] + 12 + 2.0 * dc[r] for r in rows]
     vcols = [c for c in range(nb) if dv[c] != 1]
     chk = balance(rows, rcost, W)
-    vt_pair = var_schedule(vcols, dv, W, pairs=True)
-    vt_single = var_schedule(vcols, dv, W, pairs=False)
+    vt = var_schedule(vcols, dv, W)
     bw = lpt(list(range(nb)), [1.0] * nb, W)
     col_blocks = [[i for i, b in enumerate(blocks) if b[1] == c] for c in range(nb)]
     col_ptr = [0]
@@ -284,18 +283,15 @@ def gen(name, base, z, reg_edges=True, cap=None, report=None):
     s += arr("COL_SHIFT", col_shift)
     s += arr("CHK_PTR", cp)
     s += arr("CHK_ROWS", cl)
-    for pre, sched in (("VT", vt_pair), ("VS", vt_single)):
-        # per wave: the distinct columns of its tasks (LLRs, init, shifts), then the tasks
-        # (column A, column B or -1, outputs [lo, hi)); VT pairs columns on v_pk_add_f32, VS does not
-        vp, vl = flat([sorted({t[0] for t in p} | {t[1] for t in p if t[1] >= 0}) for p in sched])
-        tp, tl = flat(sched)
-        s += arr(f"{pre}_COL_PTR", vp)
-        s += arr(f"{pre}_COLS", vl)
-        s += arr(f"{pre}_PTR", tp)
-        s += arr(f"{pre}_A", [t[0] for t in tl])
-        s += arr(f"{pre}_B", [t[1] for t in tl])
-        s += arr(f"{pre}_LO", [t[2] for t in tl])
-        s += arr(f"{pre}_HI", [t[3] for t in tl])
+    # per wave: the distinct columns of its tasks (LLRs, init, shifts), then the tasks (column A,
+    # column B or -1: a pair shares v_pk_add_f32)
+    vp, vl = flat([sorted({t[0] for t in p} | {t[1] for t in p if t[1] >= 0}) for p in vt])
+    tp, tl = flat(vt)
+    s += arr("VT_COL_PTR", vp)
+    s += arr("VT_COLS", vl)
+    s += arr("VT_PTR", tp)
+    s += arr("VT_A", [t[0] for t in tl])
+    s += arr("VT_B", [t[1] for t in tl])
     s += arr("BW_PTR", bp)
     s += arr("BW_COLS", bl)
     if reg_edges:
@@ -303,7 +299,7 @@ def gen(name, base, z, reg_edges=True, cap=None, report=None):
         # shifts in the order of ROW_SHIFT / COL_SHIFT, per edge the index into the wave's msg[]
         # (-1: the message lives in its LDS slot), rows per wave.  Columns stay on VT's waves.
         cap = REG_EDGE_CAP if cap is None else cap
-        rho, rchk, reg, info = reg_edge_schedule(blocks, z, mb, dv, row_ptr, rcost, vt_pair, cap)
+        rho, rchk, reg, info = reg_edge_schedule(blocks, z, mb, dv, row_ptr, rcost, vt, cap)
         rshift = [(b[2] + rho[b[0]]) % z for b in blocks]
         ridx = [-1] * len(blocks)
         for w in range(W):
@@ -323,14 +319,13 @@ def gen(name, base, z, reg_edges=True, cap=None, report=None):
             c = dict(zip(rows, rcost))
             report[name] = dict(info, rho=rho, nreg=[len(x) for x in reg], rows=rchk,
                                 chk_old=[sum(c[r] for r in p) for p in chk],
-                                var_old=[sum(var_task_cost(dv[a], dv[b] if b >= 0 else 0, lo, hi)
-                                             for a, b, lo, hi in p) for p in vt_pair])
+                                var_old=[sum(var_task_cost(dv[a], dv[b] if b >= 0 else 0) for a, b in p) for p in vt])
     s += "};\n\n"
     return s
 
 
 def n_min_ops(d):
-    """half-rate min / med3 ops for the two smallest of d magnitudes (flood.hip two_smallest)"""
+    """half-rate min / med3 ops for the two smallest of d magnitudes (flood_dev.hpp two_smallest)"""
     if d <= 1:
         return 0
     if d == 2:
@@ -340,7 +335,7 @@ def n_min_ops(d):
 
 def direct_row_cost(d, nout):
     """SIMD pipe cycles of a min-sum row of degree d <= DIRECT_DC with nout outputs in the direct
-    form (flood_dev.hpp direct_row), same unit costs as above: 4.1 per half-rate min / minimum3,
+    form (flood_fixed.hpp direct_row), same unit costs as above: 4.1 per half-rate min / minimum3,
     2.2 per full-rate multiply / xor / bitop3, 2.0 per edge.
     d <= 4: per output a minimum over the other inputs, their sign xor, alpha * min, sign merge.
     d >= 5: per row d // 2 pair minima, the parity (one 3-input xor per two inputs) and alpha's
@@ -352,70 +347,52 @@ def direct_row_cost(d, nout):
     return row + out * nout + 2.0 * d
 
 
-def var_task_ops(DA, DB, lo, hi):
-    """Instruction counts of a variable task (flood_dev.hpp FixedBody::task): outputs [lo, hi) of
+def var_task_ops(DA, DB):
+    """Instruction counts of a variable task (flood_fixed.hpp FixedBody::task): every output of
     column A (degree DA) and, when DB > 0, of column B (degree DB <= DA) on v_pk_add_f32 pairs.
     Per output e: acc[e] = P_e, then + c_J for J = e + 1 .. D - 1 (the reference's ascending
-    exclusive sum, traditional_decoders.py:235-250); prefix adds P_J -> P_{J+1} as far as an output
-    or an APP (the column's last prefix) needs them.  Returns (pk adds, scalar adds, LDS reads,
-    LDS writes, APPs)."""
-    hasB = DB > 0 and lo < DB
-    if not hasB:
-        DB = 0
-    nprefA = DA if hi == DA else max(hi - 1, 0)
-    blast = hasB and lo <= DB - 1 < hi  # the task holding B's last output also takes B's APP
-    npref = max(nprefA, DB if blast else 0)
+    exclusive sum, traditional_decoders.py:235-250); the prefix adds P_J -> P_{J+1} run to the APP
+    (the column's last prefix).  Returns (pk adds, scalar adds, LDS reads, LDS writes, APPs)."""
     pk = sc = 0
-    for J in range(DA):
-        for e in range(lo, min(J, hi)):
-            if J < DB:
-                pk += 1
-            else:
-                sc += 1
-        if J < npref:
-            if J < DB:
-                pk += 1
-            else:
-                sc += 1
-    writes = (hi - lo) + (max(0, min(hi, DB) - lo) if hasB else 0)
-    return pk, sc, DA + DB, writes, int(hi == DA) + int(blast)
+    for J in range(DA):  # c_J goes to the outputs e < J and to the prefix
+        if J < DB:
+            pk += J + 1
+        else:
+            sc += J + 1
+    return pk, sc, DA + DB, DA + DB, 1 + int(DB > 0)
 
 
-def var_task_cost(DA, DB, lo, hi):
+def var_task_cost(DA, DB):
     """Cycles of a variable task inside the running kernel: least squares over the measured phase
     times of both schedules (tools/flood_timeline.py on the timeline builds, profiles/r04_flood_timeline_*):
     8.2 per v_pk_add_f32 (its dependent chains issue slower than the 2.6-cycle ubench rate), 4.85
     per v_add_f32, 18.1 per LDS read or write, 33.6 per task."""
-    pk, sc, rd, wr, apps = var_task_ops(DA, DB, lo, hi)
+    pk, sc, rd, wr, apps = var_task_ops(DA, DB)
     return 8.21 * pk + 4.85 * sc + 18.12 * (rd + wr) + 33.6
 
 
-def var_schedule(vcols, dv, w, pairs=True):
+def var_schedule(vcols, dv, w):
     """Variable tasks per wave.  Columns sorted by degree; every pattern of pairing neighbours in
-    that order (pairs=True; a pair's exclusive sums share v_pk_add_f32 instructions, the smaller
-    column's adds riding along for free), each balanced over the waves (LPT + move / swap
-    refinement); the smallest makespan wins (ties: least total cost).  A column is never split by
-    output range over two waves: every output reads all of the column's messages and is written in
-    place, so a split column's writes would race the other wave's reads within the phase.
-    Returns [[(A, B or -1, 0, degree of A)]] per wave."""
+    that order (a pair's exclusive sums share v_pk_add_f32 instructions, the smaller column's adds
+    riding along for free), each balanced over the waves (LPT + move / swap refinement); the
+    smallest makespan wins (ties: least total cost).  A column is always one task on one wave:
+    every output reads all of the column's messages and is written in place, so a split column's
+    writes would race the other reads within the phase.
+    Returns [[(A, B or -1)]] per wave."""
     cols = sorted(vcols, key=lambda c: (-dv[c], c))
     n = len(cols)
-    patterns = [[]]
-    if pairs:
-        def pats(i):
-            if i >= n:
-                return [[]]
-            out = [[(cols[i],)] + p for p in pats(i + 1)]
-            if i + 1 < n:
-                out += [[(cols[i], cols[i + 1])] + p for p in pats(i + 2)]
-            return out
-        patterns = pats(0)
-    else:
-        patterns = [[(c,) for c in cols]]
+
+    def pats(i):
+        if i >= n:
+            return [[]]
+        out = [[(cols[i],)] + p for p in pats(i + 1)]
+        if i + 1 < n:
+            out += [[(cols[i], cols[i + 1])] + p for p in pats(i + 2)]
+        return out
     best = None
-    for pat in patterns:
-        t = [(u[0], u[1] if len(u) > 1 else -1, 0, dv[u[0]]) for u in pat]
-        cost = [var_task_cost(dv[a], dv[b] if b >= 0 else 0, lo, hi) for a, b, lo, hi in t]
+    for pat in pats(0):
+        t = [(u[0], u[1] if len(u) > 1 else -1) for u in pat]
+        cost = [var_task_cost(dv[a], dv[b] if b >= 0 else 0) for a, b in t]
         per = balance(t, cost, w)
         c = dict(zip(t, cost))
         cur = (max(sum(c[x] for x in p) for p in per), sum(cost), per)

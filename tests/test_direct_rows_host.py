@@ -4,7 +4,7 @@ compared bit for bit (no GPU).
 select form (rows of degree > LDPC_DIRECT_DC, and the parent of the direct form):
     m1, m2 = the two smallest magnitudes; par = xor of all sign bits
     c2v_e = ((alpha * (|x_e| == m1 ? m2 : m1)) ^ par) ^ sign(x_e)
-direct form (flood_dev.hpp direct_row):
+direct form (flood_fixed.hpp direct_row):
     degree <= 4:  c2v_e = (alpha * min_{e' != e} |x_e'|) ^ (xor_{e' != e} sign(x_e'))
     degree >= 5:  pair minima shared by the row, the row's parity folded into alpha's sign:
                   c2v_e = ((alpha ^ par) * min(|partner|, other pairs / odd input)) ^ sign(x_e)

@@ -1,7 +1,7 @@
 """Fixed flood kernel, min-sum: the direct check update of rows of degree <= 5 (GPU).
 
 The fixed kernel's fast check path writes every output of a short row straight from the other
-inputs (flood_dev.hpp direct_row); the table-driven kernel keeps the two-minimum / select form and
+inputs (flood_fixed.hpp direct_row); the table-driven kernel keeps the two-minimum / select form and
 the oracle restates the reference.  All three must give the same decisions, exactly, on inputs
 that keep decisions sensitive (low SNR), that tie at the minimum in most rows (a three-level
 magnitude grid), and that switch a workgroup to the slow path at the start (zeros, NaN) or in a

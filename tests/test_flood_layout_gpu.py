@@ -1,7 +1,7 @@
 """The fixed-schedule flooding kernel's alternating slot layout (GPU).
 
 A slot of flood_fixed_kernel is variable-indexed after a variable phase (and after init) and
-check-indexed after a check phase; both phases read rotated and store own-lane (flood_dev.hpp,
+check-indexed after a check phase; both phases read rotated and store own-lane (flood_fixed.hpp,
 "Slots").  A wrong rotation, or a store of a wave that overtakes a read of another lane of the same
 wave, corrupts messages from the first iteration on, so the cases here are the smallest that show
 it: both fixed codes, a lone frame / one full lane vector / tail workgroups, and 1, 2, 3 and 10

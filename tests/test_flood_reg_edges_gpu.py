@@ -1,9 +1,9 @@
 """Fixed flood kernel: messages of lane-local edges held in registers (GPU).
 
-With LDPC_REG_EDGES the fixed kernel runs on relabelled checks (normalised shifts) and keeps the
-message of every register edge (gen/fixed_codes.hpp RE_ROW_REG / RE_COL_REG) in a VGPR instead of
-an LDS slot (flood_dev.hpp msg[]).  The table-driven kernel and the oracle know nothing of either,
-so all three must agree exactly: on noisy frames at -3 dB, on a three-level magnitude grid that
+The fixed min-sum kernel runs on relabelled checks (normalised shifts) and keeps the message of
+every register edge (gen/fixed_codes.hpp RE_ROW_REG / RE_COL_REG) in a VGPR instead of an LDS
+slot (flood_fixed.hpp reg_edges(), msg[]).  The table-driven kernel and the oracle know nothing of
+either, so all three must agree exactly: on noisy frames at -3 dB, on a three-level magnitude grid that
 ties at the minimum in most rows, and on frames that put 0.0, +inf, -inf and NaN on variables of
 columns that own a register edge, next to an ordinary frame of the same workgroup, so that the
 exact (slow) check rows read and write msg[] and the sticky flag rises from a register v2c."""

@@ -24,7 +24,7 @@ from reg_edges_util import parse_header
 
 ALPHA = np.float32(0.75)
 SIGN = np.uint32(0x80000000)
-DIRECT_DC = 6  # LDPC_DIRECT_DC of csrc/flood_dev.hpp
+DIRECT_DC = 6  # LDPC_DIRECT_DC of csrc/flood_fixed.hpp
 ITERS = (1, 2, 3, 10)
 
 

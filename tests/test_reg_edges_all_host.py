@@ -2,7 +2,7 @@
 
 tests/test_reg_edges_host.py checks that the RE_* tables follow the rule.  Here: the generator's cap
 no longer binds, so the tables hold what the search finds (44 edges at Z = 32, 58 at Z = 4), and
-the per-instance cap of csrc/flood_dev.hpp (FxPlan<G, WV, CAP>: the first CAP entries of a wave's
+the per-instance cap of csrc/flood_fixed.hpp (FxPlan<G, WV, CAP, REG>: the first CAP entries of a wave's
 msg[] order stay register edges, the others fall back to their LDS slot) cuts a well-formed
 sub-schedule out of them for any CAP: dense msg[] indices, the dropped edges slot edges of shift 0."""
 import os
@@ -29,7 +29,7 @@ def tables():
 
 
 def slow_caps():
-    src = open(os.path.join(PKG, "csrc", "flood_dev.hpp")).read()
+    src = open(os.path.join(PKG, "csrc", "flood_fixed.hpp")).read()
     return {m.group(1): int(m.group(2)) for m in re.finditer(r"#define (LDPC_SLOW_REG_EDGES\w*) (\d+)", src)}
 
 

@@ -1,5 +1,6 @@
 # Timeline build of the flooding decoders (-DLDPC_TIMELINE: s_memtime per wave per phase, see
-# flood_dev.hpp) into ldpc_neural_decoder/_lib/variants/timeline<suffix>.so; extra flags pass through.
+# flood_dev.hpp; entry / exit stamps: flood_fixed.hpp) into ldpc_neural_decoder/_lib/variants/timeline<suffix>.so;
+# extra flags pass through.
 # usage: bash tools/build_timeline.sh [suffix] [-DFOO=1 ...]; select with LDPC_AMD_LIB=<path>
 set -e
 cd "$(dirname "$0")/../ldpc-neuralnetwork-decoder_amd"
