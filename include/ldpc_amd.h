@@ -208,6 +208,23 @@ int ldpc_gnn_plan_create_csr(int64_t E, const int32_t *h_v_ptr, const int32_t *h
                              const int32_t *h_c_ptr, const int32_t *h_c_col, const float *h_c_val,
                              ldpc_gnn_plan **out);
 int ldpc_gnn_plan_destroy(ldpc_gnn_plan *p);
+/* The tables a plan uploads, as host words (for unit tests; no device is touched).  The arguments of
+ * ldpc_gnn_plan_create / _create_csr, then a buffer of `capacity` 32-bit words.  Returns the words
+ * needed (or a negative error, as the create call would) and fills h_words when capacity holds them
+ * (h_words may be NULL to ask for the size).  Layout: the counts, one length per section, then the
+ * sections in the order the plan uploads them; float tables are stored as their bits.
+ * ldpc_gnn_plan_tables: 12 counts n_gtiles, n_gtiles_v1, n_gtiles_v, n_ptiles, n_ptiles_v,
+ *   n_ptiles_v1, n_mtiles, n_mtiles_v1, n_ctiles, ct_aligned, n_rw, rw_d1; 17 sections vgroup,
+ *   cgroup, vg_ptr, vg_mem, cg_ptr, cg_mem, inv (inv_v | inv_c), gt_meta, gt_grp, gt_mem, pt_meta,
+ *   pt_grp, pt_deg, pt_mem, mt_perm, ct_m0, rw_meta (csrc/gnn.hpp documents each).
+ * ldpc_gnn_plan_tables_csr: 3 counts E, nnz of the var side, nnz of the check side; 5 sections
+ *   tab (vgroup cgroup vg_ptr vg_mem cg_ptr cg_mem), inv, w (vg_w cg_w 0), tt (vt_ptr vt_mem ct_ptr
+ *   ct_mem: the transposes), tw (vt_w ct_w 0). */
+int64_t ldpc_gnn_plan_tables(int64_t E, int n_vgroups, const int32_t *h_vgroup, int n_cgroups,
+                             const int32_t *h_cgroup, int32_t *h_words, int64_t capacity);
+int64_t ldpc_gnn_plan_tables_csr(int64_t E, const int32_t *h_v_ptr, const int32_t *h_v_col, const float *h_v_val,
+                                 const int32_t *h_c_ptr, const int32_t *h_c_col, const float *h_c_val,
+                                 int32_t *h_words, int64_t capacity);
 /* Hybrid GNN (CustomVariableMessageGNNDecoder.forward, models/message_gnn_decoder.py:798-879 with
  * CustomVariableMessageGNNLayer.forward :672-755).  The reference cannot run it;
  * the semantics this build defines (check-side MLP + the layer's own output head, min-sum variable

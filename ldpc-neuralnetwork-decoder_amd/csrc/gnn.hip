@@ -1648,60 +1648,62 @@ struct Ws {
     uint32_t *xmax[2], *hmax, *gmax_v, *gmax_c;  // wide path: each row's largest |value| (f16 splits)
     float *S, *memb;  // row walk (H = 64, plan rw_*): per-check feature sums (B, Gc, H), mean type embeddings (L, Gc, H)
     float *memb_v;    // ... and per var group (L, Gv, H)
+    float *v2c;       // hybrid decoder: the variable update's messages (B, E)
     int32_t *csr;
     int64_t bytes;
 };
 
+// The fp32 forwards' buffers, taken in the order they lie in the workspace.
 // train: the training forward (d_saved), which never takes the wide path -- the backward
-// (gnn_train.hip) recomputes h and the ReLU masks with gnn_mlp_tiled_kernel's fma chains
-Ws carve(const ldpc_gnn_plan *p, int H, int N, int64_t B, int layers, int precision, void *base, bool train = false) {
+// (gnn_train.hip) recomputes h and the ReLU masks with gnn_mlp_tiled_kernel's fma chains.
+// hybrid: the hybrid decoder's v2c follows everything else.
+Ws carve(const ldpc_gnn_plan *p, int H, int N, int64_t B, int layers, void *base, bool train = false,
+         bool hybrid = false) {
     Ws w{};
-    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
+    GnnArena a(base);
     const int64_t es = 4;  // bytes per stored feature (fp32 path)
-    (void)precision;
     const bool wide = wide_on(p, H) && !train;  // the last layer's rows are stored too (its head reads them)
-    const int64_t xb = layers > 1 || wide ? al(B * p->E * H * es) : 0;
-    const int64_t xb2 = layers > 2 || (wide && layers > 1) ? xb : 0;
-    const int64_t mv = al(B * (int64_t)p->Gv * H * es), mc = al(B * (int64_t)p->Gc * H * es);
-    const int64_t vs = al(B * p->E * 4), cs = al(gnn_csr_ints(p->E, N) * 4);
-    char *c = static_cast<char *>(base);
-    w.xa = reinterpret_cast<float *>(c);
-    w.xb = reinterpret_cast<float *>(c + xb);
-    w.Mv = reinterpret_cast<float *>(c + xb + xb2);
-    w.Mc = reinterpret_cast<float *>(c + xb + xb2 + mv);
-    w.msg_out = reinterpret_cast<float *>(c + xb + xb2 + mv + mc);
-    w.csr = reinterpret_cast<int32_t *>(c + xb + xb2 + mv + mc + vs);
+    const int64_t x = B * p->E * H * es, mv = B * (int64_t)p->Gv * H * es, mc = B * (int64_t)p->Gc * H * es;
+    // the feature ping-pong: a buffer no layer writes takes no bytes (its pointer is the next buffer's)
+    w.xa = a.take<float>(layers > 1 || wide ? x : 0);
+    w.xb = a.take<float>(layers > 2 || (wide && layers > 1) ? x : 0);
+    w.Mv = a.take<float>(mv);
+    w.Mc = a.take<float>(mc);
+    w.msg_out = a.take<float>(B * p->E * 4);
+    w.csr = a.take<int32_t>(gnn_csr_ints(p->E, N) * 4);
     // H != 64 (gnn_mlp_tiled_kernel): every layer's transposed MLP weights, 6 H^2 floats each
     // (formed once per call, before the frame halves fork onto two streams)
-    const int64_t wtb = H != 64 && H <= kTiledMaxH && !wide ? al(6LL * H * H * 4 * layers) : 0;
-    w.wt = wtb ? reinterpret_cast<float *>(c + xb + xb2 + mv + mc + vs + cs) : nullptr;
-    const int64_t rwb = H == 64 && p->n_rw > 0 && layers > 1 ? mc : 0;
-    const int64_t mbb = rwb ? al((int64_t)layers * (p->Gc + p->Gv) * H * es) : 0;
-    char *r = c + xb + xb2 + mv + mc + vs + cs + wtb;
-    w.S = rwb ? reinterpret_cast<float *>(r) : nullptr;
-    w.memb = rwb ? reinterpret_cast<float *>(r + rwb) : nullptr;
-    w.memb_v = rwb ? w.memb + (int64_t)layers * p->Gc * H : nullptr;
-    const int64_t hb = wide ? al(B * p->E * 2 * H * es) : 0;
-    char *q = r + rwb + mbb;
-    w.Pv = wide ? reinterpret_cast<float *>(q) : nullptr;
-    w.Pc = wide ? reinterpret_cast<float *>(q + mv) : nullptr;
-    w.hbuf = wide ? reinterpret_cast<float *>(q + mv + mc) : nullptr;
-    // row maxima: x (two, with the feature ping-pong), h, group rows: 4 B per row
-    const int64_t rm = al(B * p->E * 4), gmv = al(B * (int64_t)p->Gv * 4), gmc = al(B * (int64_t)p->Gc * 4);
-    char *z = q + (wide ? mv + mc + hb : 0);
-    w.xmax[0] = wide ? reinterpret_cast<uint32_t *>(z) : nullptr;
-    w.xmax[1] = wide ? reinterpret_cast<uint32_t *>(z + rm) : nullptr;
-    w.hmax = wide ? reinterpret_cast<uint32_t *>(z + 2 * rm) : nullptr;
-    w.gmax_v = wide ? reinterpret_cast<uint32_t *>(z + 3 * rm) : nullptr;
-    w.gmax_c = wide ? reinterpret_cast<uint32_t *>(z + 3 * rm + gmv) : nullptr;
-    const int64_t fib = wide ? al(gnn_wide_fused_bytes(H, layers)) : 0, feb = fib ? al(2LL * layers * 4) : 0;
-    char *f = z + (wide ? 3 * rm + gmv + gmc : 0);
-    w.wimg = fib ? f : nullptr;
-    w.wexp = fib ? reinterpret_cast<int *>(f + fib) : nullptr;
-    const int64_t wmb = wide ? al((int64_t)layers * (p->Gv + p->Gc) * H * 4) : 0;
-    w.wmemb = wmb ? reinterpret_cast<float *>(f + fib + feb) : nullptr;
-    w.bytes = xb + xb2 + mv + mc + vs + cs + wtb + rwb + mbb + (wide ? mv + mc + hb + 3 * rm + gmv + gmc : 0) + fib + feb + wmb;
+    if (H != 64 && H <= kTiledMaxH && !wide) w.wt = a.take<float>(6LL * H * H * 4 * layers);
+    if (H == 64 && p->n_rw > 0 && layers > 1 && B > 0) {  // row walk
+        w.S = a.take<float>(mc);
+        w.memb = a.take<float>((int64_t)layers * (p->Gc + p->Gv) * H * es);
+        w.memb_v = w.memb + (int64_t)layers * p->Gc * H;
+    }
+    if (wide) {
+        w.Pv = a.take<float>(mv);
+        w.Pc = a.take<float>(mc);
+        w.hbuf = a.take<float>(B * p->E * 2 * H * es);
+        // row maxima: x (two, with the feature ping-pong), h, group rows: 4 B per row
+        w.xmax[0] = a.take<uint32_t>(B * p->E * 4);
+        w.xmax[1] = a.take<uint32_t>(B * p->E * 4);
+        w.hmax = a.take<uint32_t>(B * p->E * 4);
+        w.gmax_v = a.take<uint32_t>(B * (int64_t)p->Gv * 4);
+        w.gmax_c = a.take<uint32_t>(B * (int64_t)p->Gc * 4);
+        if (const int64_t fused = gnn_wide_fused_bytes(H, layers)) {
+            w.wimg = a.take<char>(fused);
+            w.wexp = a.take<int>(2LL * layers * 4);
+        }
+        w.wmemb = a.take<float>((int64_t)layers * (p->Gv + p->Gc) * H * 4);
+    }
+    if (hybrid) w.v2c = a.take<float>(B * p->E * 4);
+    w.bytes = a.bytes;
     return w;
+}
+
+// The hybrid decoder's workspace: at least 3 layers keep both feature buffers (H != 64: the tiled
+// kernel's transposed weights, never the wide path), + v2c (B, E)
+Ws carve_hybrid(const ldpc_gnn_plan *p, int H, int N, int64_t B, int layers, void *base) {
+    return carve(p, H, N, B, std::max(layers, 3), base, H != kMfmaH, true);
 }
 
 // ------------------------------------------------------------------------ hybrid GNN (CustomVariable*)
@@ -2061,348 +2063,6 @@ int ldpc::gnn_output(const float *d_msg_out, const int32_t *d_ints, const float 
     return LDPC_OK;
 }
 
-extern "C" int ldpc_gnn_plan_create(int64_t E, int n_vgroups, const int32_t *h_vgroup, int n_cgroups,
-                                    const int32_t *h_cgroup, ldpc_gnn_plan **out) {
-    if (!out) return fail(LDPC_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (E <= 0 || n_vgroups <= 0 || n_cgroups <= 0 || !h_vgroup || !h_cgroup)
-        return fail(LDPC_EINVAL, "bad GNN plan arguments");
-    std::vector<int32_t> vptr(n_vgroups + 1, 0), cptr(n_cgroups + 1, 0), vmem(E), cmem(E);
-    for (int64_t m = 0; m < E; ++m) {
-        if (h_vgroup[m] < 0 || h_vgroup[m] >= n_vgroups || h_cgroup[m] < 0 || h_cgroup[m] >= n_cgroups)
-            return fail(LDPC_EINVAL, "group label out of range");
-        vptr[h_vgroup[m] + 1]++;
-        cptr[h_cgroup[m] + 1]++;
-    }
-    for (int g = 0; g < n_vgroups; ++g) vptr[g + 1] += vptr[g];
-    for (int g = 0; g < n_cgroups; ++g) cptr[g + 1] += cptr[g];
-    {
-        std::vector<int32_t> fv(vptr.begin(), vptr.end() - 1), fc(cptr.begin(), cptr.end() - 1);
-        for (int64_t m = 0; m < E; ++m) {  // members in ascending message order
-            vmem[fv[h_vgroup[m]]++] = (int32_t)m;
-            cmem[fc[h_cgroup[m]]++] = (int32_t)m;
-        }
-    }
-    std::vector<float> inv(n_vgroups + n_cgroups);
-    for (int g = 0; g < n_vgroups; ++g) {
-        const int d = vptr[g + 1] - vptr[g];
-        inv[g] = d ? 1.0f / (float)d : 0.0f;
-    }
-    for (int g = 0; g < n_cgroups; ++g) {
-        const int d = cptr[g + 1] - cptr[g];
-        inv[n_vgroups + g] = d ? 1.0f / (float)d : 0.0f;
-    }
-    // bf16 path: group tiles of 8 groups of one degree (gnn.hpp), var side then check side
-    std::vector<int32_t> gt_meta, gt_grp, gt_mem;
-    auto add_tiles = [&](const std::vector<int32_t> &ptr, const std::vector<int32_t> &mem, int ngroups, int gbase) {
-        std::vector<int32_t> order;
-        for (int g = 0; g < ngroups; ++g)
-            if (ptr[g + 1] > ptr[g]) order.push_back(g);  // a group with no messages is never read
-        std::stable_sort(order.begin(), order.end(),
-                         [&](int a, int b) { return ptr[a + 1] - ptr[a] < ptr[b + 1] - ptr[b]; });
-        for (size_t i = 0; i < order.size();) {
-            const int d = ptr[order[i] + 1] - ptr[order[i]];
-            size_t n = 0;
-            while (n < 8 && i + n < order.size() && ptr[order[i + n] + 1] - ptr[order[i + n]] == d) ++n;
-            gt_meta.push_back(d);
-            gt_meta.push_back((int32_t)gt_mem.size());
-            for (int k = 0; k < d; ++k)
-                for (size_t q = 0; q < 8; ++q)
-                    gt_mem.push_back(q < n ? mem[ptr[order[i + q]] + k] : mem[ptr[order[i]] + k]);
-            for (size_t q = 0; q < 8; ++q) gt_grp.push_back(q < n ? gbase + order[i + q] : -1);
-            i += n;
-        }
-    };
-    add_tiles(vptr, vmem, n_vgroups, 0);
-    int n_v1 = 0;  // var tiles come first, sorted by degree: the degree-1 ones lead
-    while (2 * n_v1 < (int)gt_meta.size() && gt_meta[2 * n_v1] == 1) ++n_v1;
-    const int n_gt_v = (int)(gt_meta.size() / 2);
-    add_tiles(cptr, cmem, n_cgroups, n_vgroups);
-    // bf16 MLP tiles (gnn.hpp ct_m0): whole check groups when each is a contiguous message run of
-    // at most 32 (greedy, in message order), else plain 32-message tiles
-    bool aligned = true;
-    for (int g = 0; g < n_cgroups && aligned; ++g) {
-        const int d = cptr[g + 1] - cptr[g];
-        aligned = d <= 32 && (d == 0 || cmem[cptr[g + 1] - 1] - cmem[cptr[g]] == d - 1);
-    }
-    std::vector<int32_t> ct_m0{0};
-    if (aligned) {
-        int64_t m = 0;
-        while (m < E) {
-            const int g = h_cgroup[m];
-            const int d = cptr[g + 1] - cptr[g];  // the group's run starts at m (contiguous, ascending)
-            if (m + d - ct_m0.back() > 32) ct_m0.push_back((int32_t)m);
-            m += d;
-        }
-    } else {
-        for (int64_t m = 32; m < E; m += 32) ct_m0.push_back((int32_t)m);
-    }
-    ct_m0.push_back((int32_t)E);
-    // fp32 row walk: check tile groups (gnn.hpp rw_*), used when they fill >= 90 % of their tiles
-    std::vector<int32_t> rw_meta, rw_cg;
-    bool rw_d1 = true, rw_contig = true;  // rw_contig: lane k of a unit holds check group first + k
-    if (aligned) {
-        auto vdeg1 = [&](int64_t m) { return vptr[h_vgroup[m] + 1] - vptr[h_vgroup[m]] == 1; };
-        int64_t m = 0, slots = 0, d1_msgs = 0, d1_in_tiles = 0;
-        for (int64_t q = 0; q < E; ++q) d1_msgs += vdeg1(q);
-        while (m < E) {
-            const int d = cptr[h_cgroup[m] + 1] - cptr[h_cgroup[m]];
-            const int64_t m0 = m;
-            int n = 0;
-            while (n < 32 && m < E && cptr[h_cgroup[m] + 1] - cptr[h_cgroup[m]] == d) {
-                rw_cg.push_back(h_cgroup[m]);
-                ++n;
-                m += d;
-            }
-            for (int k = n; k < 32; ++k) rw_cg.push_back(-1);
-            int32_t mask = 0;
-            for (int i = 0; i < d; ++i) {
-                bool all = true;
-                for (int k = 0; k < n && all; ++k) all = vdeg1(m0 + (int64_t)k * d + i);
-                if (all) {
-                    mask |= (int32_t)(1u << i);
-                    d1_in_tiles += n;
-                }
-            }
-            for (int k = 1; k < n; ++k) rw_contig = rw_contig && rw_cg[rw_cg.size() - 32 + k] == rw_cg[rw_cg.size() - 32] + k;
-            rw_meta.insert(rw_meta.end(), {(int32_t)m0, n, d, mask, rw_cg[rw_cg.size() - 32], 0, 0, 0});
-            slots += 32LL * d;
-        }
-        rw_d1 = d1_in_tiles == d1_msgs;
-        if (!rw_d1)
-            for (size_t c = 0; c < rw_meta.size(); c += 8) rw_meta[c + 3] = 0;
-        if ((double)E < 0.9 * (double)slots || !rw_contig) rw_meta.clear();
-        rw_cg.clear();
-    }
-    // fp32 path: projection tiles of 32 groups of one side (gnn.hpp), each side sorted by degree
-    std::vector<int32_t> pt;  // meta [4 n] | grp [32 n] | deg [32 n] | mem
-    std::vector<int32_t> pt_meta, pt_grp, pt_deg, pt_mem;
-    auto add_ptiles = [&](const std::vector<int32_t> &ptr, const std::vector<int32_t> &mem, int ngroups, int side) {
-        std::vector<int32_t> order;
-        for (int g = 0; g < ngroups; ++g)
-            if (ptr[g + 1] > ptr[g]) order.push_back(g);
-        std::stable_sort(order.begin(), order.end(),
-                         [&](int a, int b) { return ptr[a + 1] - ptr[a] < ptr[b + 1] - ptr[b]; });
-        for (size_t i = 0; i < order.size(); i += 32) {
-            const size_t n = std::min<size_t>(32, order.size() - i);
-            int dmax = 0;
-            for (size_t q = 0; q < n; ++q) dmax = std::max(dmax, ptr[order[i + q] + 1] - ptr[order[i + q]]);
-            pt_meta.insert(pt_meta.end(), {side, dmax, (int32_t)pt_mem.size(), 0});
-            for (int k = 0; k <= dmax; ++k)  // one padding row: the kernel reads members in pairs
-                for (size_t q = 0; q < 32; ++q) {
-                    const int g = q < n ? order[i + q] : -1;
-                    pt_mem.push_back(g >= 0 && k < ptr[g + 1] - ptr[g] ? mem[ptr[g] + k] : 0);
-                }
-            for (size_t q = 0; q < 32; ++q) {
-                pt_grp.push_back(q < n ? order[i + q] : -1);
-                pt_deg.push_back(q < n ? ptr[order[i + q] + 1] - ptr[order[i + q]] : 0);
-            }
-        }
-    };
-    add_ptiles(vptr, vmem, n_vgroups, 0);
-    const int n_ptiles_v = (int)(pt_meta.size() / 4);
-    int n_ptiles_v1 = 0;  // leading var tiles of degree-1 groups only (padding has degree 0)
-    while (n_ptiles_v1 < n_ptiles_v &&
-           std::all_of(pt_deg.begin() + 32 * n_ptiles_v1, pt_deg.begin() + 32 * (n_ptiles_v1 + 1),
-                       [](int32_t d) { return d <= 1; }))
-        ++n_ptiles_v1;
-    add_ptiles(cptr, cmem, n_cgroups, 1);
-    // bf16 projected MLP: degree-1 var groups' messages first, each part padded to whole tiles
-    std::vector<int32_t> mperm;
-    auto vdeg = [&](int64_t m) { return vptr[h_vgroup[m] + 1] - vptr[h_vgroup[m]]; };
-    for (int64_t m = 0; m < E; ++m)
-        if (vdeg(m) == 1) mperm.push_back((int32_t)m);
-    while (mperm.size() % 32) mperm.push_back(-1);
-    const int n_mtiles_v1 = (int)(mperm.size() / 32);
-    for (int64_t m = 0; m < E; ++m)
-        if (vdeg(m) != 1) mperm.push_back((int32_t)m);
-    while (mperm.size() % 32) mperm.push_back(-1);
-    pt.insert(pt.end(), pt_meta.begin(), pt_meta.end());
-    pt.insert(pt.end(), pt_grp.begin(), pt_grp.end());
-    pt.insert(pt.end(), pt_deg.begin(), pt_deg.end());
-    pt.insert(pt.end(), pt_mem.begin(), pt_mem.end());
-    pt.insert(pt.end(), mperm.begin(), mperm.end());
-    std::vector<int32_t> blob;
-    blob.insert(blob.end(), h_vgroup, h_vgroup + E);
-    blob.insert(blob.end(), h_cgroup, h_cgroup + E);
-    blob.insert(blob.end(), vptr.begin(), vptr.end());
-    blob.insert(blob.end(), vmem.begin(), vmem.end());
-    blob.insert(blob.end(), cptr.begin(), cptr.end());
-    blob.insert(blob.end(), cmem.begin(), cmem.end());
-    const size_t gt_words = gt_meta.size() + gt_grp.size() + gt_mem.size();
-    auto *p = new ldpc_gnn_plan();
-    p->n_gtiles = (int)(gt_meta.size() / 2);
-    p->n_gtiles_v1 = n_v1;
-    p->E = E;
-    p->Gv = n_vgroups;
-    p->Gc = n_cgroups;
-    hipError_t e1 = hipGetDevice(&p->device);
-    hipError_t e2 = hipMalloc(&p->d_tab, blob.size() * 4);
-    hipError_t e3 = hipMalloc(&p->d_inv, inv.size() * 4);
-    hipError_t e4 = hipMalloc(&p->d_gt, gt_words * 4);
-    hipError_t e5 = hipMalloc(&p->d_pt, pt.size() * 4);
-    hipError_t e6 = hipMalloc(&p->d_ct, ct_m0.size() * 4);
-    hipError_t e7 = rw_meta.empty() ? hipSuccess : hipMalloc(&p->d_rw, rw_meta.size() * 4);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess ||
-        e6 != hipSuccess || e7 != hipSuccess) {
-        ldpc_gnn_plan_destroy(p);
-        return fail(LDPC_EHIP, "GNN plan allocation failed");
-    }
-    if (hipMemcpy(p->d_tab, blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_inv, inv.data(), inv.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_gt, gt_meta.data(), gt_meta.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_gt + gt_meta.size(), gt_grp.data(), gt_grp.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_gt + gt_meta.size() + gt_grp.size(), gt_mem.data(), gt_mem.size() * 4,
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_pt, pt.data(), pt.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_ct, ct_m0.data(), ct_m0.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (p->d_rw && hipMemcpy(p->d_rw, rw_meta.data(), rw_meta.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
-        ldpc_gnn_plan_destroy(p);
-        return fail(LDPC_EHIP, "GNN plan upload failed");
-    }
-    p->n_rw = (int)(rw_meta.size() / 8);
-    p->rw_d1 = p->n_rw > 0 && rw_d1;
-    p->rw_meta = reinterpret_cast<const int4 *>(p->d_rw);
-    p->n_ptiles = (int)(pt_meta.size() / 4);
-    p->n_ptiles_v = n_ptiles_v;
-    p->n_ptiles_v1 = n_ptiles_v1;
-    p->pt_meta = reinterpret_cast<const int4 *>(p->d_pt);
-    p->pt_grp = p->d_pt + pt_meta.size();
-    p->pt_deg = p->pt_grp + pt_grp.size();
-    p->pt_mem = p->pt_deg + pt_deg.size();
-    p->mt_perm = p->pt_mem + pt_mem.size();
-    p->n_mtiles = (int)(mperm.size() / 32);
-    p->n_mtiles_v1 = n_mtiles_v1;
-    p->n_gtiles_v = n_gt_v;
-    p->n_ctiles = (int)ct_m0.size() - 1;
-    p->ct_aligned = aligned;
-    p->ct_m0 = p->d_ct;
-    p->vgroup = p->d_tab;
-    p->cgroup = p->vgroup + E;
-    p->vg_ptr = p->cgroup + E;
-    p->vg_mem = p->vg_ptr + n_vgroups + 1;
-    p->cg_ptr = p->vg_mem + E;
-    p->cg_mem = p->cg_ptr + n_cgroups + 1;
-    p->inv_v = p->d_inv;
-    p->inv_c = p->d_inv + n_vgroups;
-    p->gt_meta = reinterpret_cast<const int2 *>(p->d_gt);
-    p->gt_grp = p->d_gt + gt_meta.size();
-    p->gt_mem = p->gt_grp + gt_grp.size();
-    *out = p;
-    return LDPC_OK;
-}
-
-// General adjacencies (message_gnn_decoder.py:93-118: any (E x E) matrix after the reference's
-// zero-pad / crop) as two CSR matrices: row m lists the messages j with A[m, j] != 0, ascending, and
-// their values.  Every message reads aggregation row m of each side, so the MLP kernels run
-// unchanged on rows that are bmm(A, c) instead of group means.
-extern "C" int ldpc_gnn_plan_create_csr(int64_t E, const int32_t *h_v_ptr, const int32_t *h_v_col, const float *h_v_val,
-                                        const int32_t *h_c_ptr, const int32_t *h_c_col, const float *h_c_val,
-                                        ldpc_gnn_plan **out) {
-    if (!out) return fail(LDPC_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (E <= 0 || E > (1 << 30) || !h_v_ptr || !h_c_ptr) return fail(LDPC_EINVAL, "bad GNN CSR plan arguments");
-    const int64_t nv = h_v_ptr[E], nc = h_c_ptr[E];
-    if (h_v_ptr[0] != 0 || h_c_ptr[0] != 0 || nv < 0 || nc < 0 || (nv && (!h_v_col || !h_v_val)) ||
-        (nc && (!h_c_col || !h_c_val)))
-        return fail(LDPC_EINVAL, "bad CSR arrays");
-    for (int64_t m = 0; m < E; ++m)
-        if (h_v_ptr[m + 1] < h_v_ptr[m] || h_c_ptr[m + 1] < h_c_ptr[m]) return fail(LDPC_EINVAL, "CSR row pointers must ascend");
-    for (int64_t i = 0; i < nv; ++i)
-        if (h_v_col[i] < 0 || h_v_col[i] >= E) return fail(LDPC_EINVAL, "CSR column out of range");
-    for (int64_t i = 0; i < nc; ++i)
-        if (h_c_col[i] < 0 || h_c_col[i] >= E) return fail(LDPC_EINVAL, "CSR column out of range");
-    std::vector<int32_t> blob;
-    blob.reserve(2 * E + 2 * (E + 1) + nv + nc);
-    for (int64_t m = 0; m < E; ++m) blob.push_back((int32_t)m);  // vgroup: own row
-    for (int64_t m = 0; m < E; ++m) blob.push_back((int32_t)m);  // cgroup: own row
-    blob.insert(blob.end(), h_v_ptr, h_v_ptr + E + 1);
-    blob.insert(blob.end(), h_v_col, h_v_col + nv);
-    blob.insert(blob.end(), h_c_ptr, h_c_ptr + E + 1);
-    blob.insert(blob.end(), h_c_col, h_c_col + nc);
-    std::vector<float> inv(2 * E, 1.0f), wts;
-    wts.insert(wts.end(), h_v_val, h_v_val + nv);
-    wts.insert(wts.end(), h_c_val, h_c_val + nc);
-    wts.push_back(0.0f);
-    // the transposes: a counting sort of the nonzeros by column, rows ascending within a column
-    std::vector<int32_t> tt;
-    std::vector<float> tw;
-    tt.reserve(2 * (E + 1) + nv + nc);
-    tw.reserve(nv + nc + 1);
-    auto transpose = [&](const int32_t *ptr, const int32_t *col, const float *val, int64_t nnz) {
-        const size_t p0 = tt.size();
-        tt.resize(p0 + E + 1, 0);
-        int32_t *tp = tt.data() + p0;
-        for (int64_t i = 0; i < nnz; ++i) tp[col[i] + 1]++;
-        for (int64_t j = 0; j < E; ++j) tp[j + 1] += tp[j];
-        std::vector<int32_t> cur(tp, tp + E), mem(nnz);
-        std::vector<float> w(nnz);
-        for (int64_t m = 0; m < E; ++m)
-            for (int32_t i = ptr[m]; i < ptr[m + 1]; ++i) {
-                const int32_t k = cur[col[i]]++;
-                mem[k] = (int32_t)m;
-                w[k] = val[i];
-            }
-        tt.insert(tt.end(), mem.begin(), mem.end());
-        tw.insert(tw.end(), w.begin(), w.end());
-    };
-    transpose(h_v_ptr, h_v_col, h_v_val, nv);
-    transpose(h_c_ptr, h_c_col, h_c_val, nc);
-    tw.push_back(0.0f);
-    auto *p = new ldpc_gnn_plan();
-    p->E = E;
-    p->Gv = (int)E;
-    p->Gc = (int)E;
-    p->weighted = true;
-    if (hipGetDevice(&p->device) != hipSuccess || hipMalloc(&p->d_tab, blob.size() * 4) != hipSuccess ||
-        hipMalloc(&p->d_inv, inv.size() * 4) != hipSuccess || hipMalloc(&p->d_w, wts.size() * 4) != hipSuccess ||
-        hipMalloc(&p->d_tt, tt.size() * 4) != hipSuccess || hipMalloc(&p->d_tw, tw.size() * 4) != hipSuccess) {
-        ldpc_gnn_plan_destroy(p);
-        return fail(LDPC_EHIP, "GNN plan allocation failed");
-    }
-    if (hipMemcpy(p->d_tab, blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_inv, inv.data(), inv.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_w, wts.data(), wts.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_tt, tt.data(), tt.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_tw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        ldpc_gnn_plan_destroy(p);
-        return fail(LDPC_EHIP, "GNN plan upload failed");
-    }
-    p->vgroup = p->d_tab;
-    p->cgroup = p->vgroup + E;
-    p->vg_ptr = p->cgroup + E;
-    p->vg_mem = p->vg_ptr + E + 1;
-    p->cg_ptr = p->vg_mem + nv;
-    p->cg_mem = p->cg_ptr + E + 1;
-    p->inv_v = p->d_inv;
-    p->inv_c = p->d_inv + E;
-    p->vg_w = p->d_w;
-    p->cg_w = p->d_w + nv;
-    p->vt_ptr = p->d_tt;
-    p->vt_mem = p->vt_ptr + E + 1;
-    p->ct_ptr = p->vt_mem + nv;
-    p->ct_mem = p->ct_ptr + E + 1;
-    p->vt_w = p->d_tw;
-    p->ct_w = p->d_tw + nv;
-    *out = p;
-    return LDPC_OK;
-}
-
-extern "C" int ldpc_gnn_plan_destroy(ldpc_gnn_plan *p) {
-    if (!p) return LDPC_OK;
-    if (p->d_tab) (void)hipFree(p->d_tab);
-    if (p->d_inv) (void)hipFree(p->d_inv);
-    if (p->d_w) (void)hipFree(p->d_w);
-    if (p->d_tt) (void)hipFree(p->d_tt);
-    if (p->d_tw) (void)hipFree(p->d_tw);
-    if (p->d_gt) (void)hipFree(p->d_gt);
-    if (p->d_pt) (void)hipFree(p->d_pt);
-    if (p->d_ct) (void)hipFree(p->d_ct);
-    if (p->d_rw) (void)hipFree(p->d_rw);
-    delete p;
-    return LDPC_OK;
-}
-
 extern "C" int64_t ldpc_gnn_weights_size(int hidden, int types, int layers) {
     if (hidden <= 0 || types <= 0 || layers <= 0) return fail(LDPC_EINVAL, "bad GNN dimensions");
     return 2LL * hidden + (int64_t)layers * gnn_layer_floats(hidden, types);
@@ -2412,11 +2072,11 @@ extern "C" int64_t ldpc_gnn_workspace_size(const ldpc_gnn_plan *p, int hidden, i
                                            int precision) {
     if (!p || hidden <= 0 || N <= 0 || B < 0 || layers <= 0) return fail(LDPC_EINVAL, "bad arguments");
     if (precision == 1) return gnn_bf16_workspace(p, N, B, layers);
-    return carve(p, hidden, N, B, layers, precision, nullptr).bytes;
+    return carve(p, hidden, N, B, layers, nullptr).bytes;
 }
 
 int64_t ldpc::gnn_fp32_train_workspace(const ldpc_gnn_plan *p, int hidden, int N, int64_t B, int layers) {
-    return carve(p, hidden, N, B, layers, 0, nullptr, true).bytes;
+    return carve(p, hidden, N, B, layers, nullptr, true).bytes;
 }
 
 // the forward writes the area only on its projected-group path (the same predicate as its `proj`)
@@ -2431,7 +2091,7 @@ int ldpc::gnn_fp32_forward(const ldpc_gnn_plan *p, int hidden, int types, int la
                            float *d_proj, bool fp32_products) {
     const int H = hidden;
     const bool train = d_saved != nullptr;
-    Ws w = carve(p, H, N, B, layers, 0, d_work, train);
+    Ws w = carve(p, H, N, B, layers, d_work, train);
     if (!d_work || work_bytes < w.bytes)
         return fail(LDPC_EINVAL, "workspace too small: need " + std::to_string(w.bytes) + " bytes");
     int cus = 0;
@@ -2660,9 +2320,7 @@ extern "C" int ldpc_gnn_forward(const ldpc_gnn_plan *p, int hidden, int types, i
 // ------------------------------------------------------------------------ hybrid GNN host side
 extern "C" int64_t ldpc_gnn_custom_var_workspace_size(const ldpc_gnn_plan *p, int hidden, int N, int64_t B, int layers) {
     if (!p || hidden <= 0 || N <= 0 || B < 0 || layers <= 0) return fail(LDPC_EINVAL, "bad arguments");
-    // carve() with at least 3 layers keeps both feature buffers (H != 64: the tiled kernel's
-    // transposed weights, never the wide path); + v2c (B, E)
-    return carve(p, hidden, N, B, std::max(layers, 3), 0, nullptr, hidden != kMfmaH).bytes + (B * p->E * 4 + 255) / 256 * 256;
+    return carve_hybrid(p, hidden, N, B, layers, nullptr).bytes;
 }
 
 namespace ldpc {
@@ -2683,8 +2341,7 @@ GnnLayer hybrid_layer(const ldpc_gnn_plan *p, int H, int types, const float *d_w
 int custom_var_forward_any(const ldpc_gnn_plan *p, int H, int types, int layers, const float *d_weights,
                            const int32_t *d_msg_type, const int32_t *d_msg_var, const float *d_llr, int N, int64_t B,
                            float *d_probs, void *d_work, hipStream_t s) {
-    Ws w = carve(p, H, N, B, std::max(layers, 3), 0, d_work, true);
-    float *v2c = reinterpret_cast<float *>(static_cast<char *>(d_work) + w.bytes);
+    const Ws w = carve_hybrid(p, H, N, B, layers, d_work);
     if (!w.wt) return fail(LDPC_EUNSUPPORTED, "hidden_dim too wide for the hybrid GNN");
     int cus = 0;
     if (int rc = gnn_num_cus(&cus)) return rc;
@@ -2693,7 +2350,7 @@ int custom_var_forward_any(const ldpc_gnn_plan *p, int H, int types, int layers,
     const int64_t R = B * p->E;
     for (int l = 0; l < layers; ++l) {
         set_layer_weights(L, gnn_layer_weights(d_weights, H, types, l));
-        L.hv2c = l > 0 ? v2c : nullptr;        // layers >= 1 read x = (v2c w_in + b_in) + F_{l-1}
+        L.hv2c = l > 0 ? w.v2c : nullptr;      // layers >= 1 read x = (v2c w_in + b_in) + F_{l-1}
         L.x_out = (l % 2 == 0) ? w.xa : w.xb;  // F
         L.wt = w.wt + 6LL * H * H * l;
         hipLaunchKernelGGL(gnn_wt_kernel, dim3((unsigned)((6LL * H * H + 255) / 256)), dim3(256), 0, s, L.w1v, L.w2v,
@@ -2704,11 +2361,11 @@ int custom_var_forward_any(const ldpc_gnn_plan *p, int H, int types, int layers,
         LDPC_CHECK_LAUNCH("gnn_group_mean_kernel (hybrid check side)");
         if (int rc = launch_tiled(L, H, R, cus, s, "gnn_mlp_tiled_kernel (hybrid check side)")) return rc;
         hipLaunchKernelGGL(custom_var_llr_kernel, dim3((unsigned)((B * N + 255) / 256)), dim3(256), 0, s, w.msg_out, w.csr,
-                           d_llr, p->E, N, B, v2c);
+                           d_llr, p->E, N, B, w.v2c);
         LDPC_CHECK_LAUNCH("hybrid GNN variable update");
         if (l == layers - 1) {
             hipLaunchKernelGGL(custom_combine_any_kernel, dim3((unsigned)((R * 16 + 255) / 256)), dim3(256), 0, s, L.x_out,
-                               v2c, d_weights, d_weights + H, H, R, L.wo, L.bo, w.msg_out);
+                               w.v2c, d_weights, d_weights + H, H, R, L.wo, L.bo, w.msg_out);
             LDPC_CHECK_LAUNCH("hybrid GNN output head");
         }
         L.x_in = L.x_out;
@@ -2739,8 +2396,7 @@ extern "C" int ldpc_gnn_custom_var_forward(const ldpc_gnn_plan *p, int hidden, i
                                       d_work, static_cast<hipStream_t>(stream));
     const int H = kMfmaH;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    Ws w = carve(p, H, N, B, std::max(layers, 3), 0, d_work);
-    float *v2c = reinterpret_cast<float *>(static_cast<char *>(d_work) + w.bytes);
+    const Ws w = carve_hybrid(p, H, N, B, layers, d_work);
     int cus = 0;
     if (int rc = gnn_num_cus(&cus)) return rc;
     const ProjKernel proj_k = select_proj(types, true, true, true);
@@ -2754,18 +2410,18 @@ extern "C" int ldpc_gnn_custom_var_forward(const ldpc_gnn_plan *p, int hidden, i
     const int64_t R = B * p->E;
     for (int l = 0; l < layers; ++l) {
         set_layer_weights(L, gnn_layer_weights(d_weights, H, types, l));
-        L.hv2c = l > 0 ? v2c : nullptr;        // layers >= 1 read x = (v2c w_in + b_in) + F_{l-1}
+        L.hv2c = l > 0 ? w.v2c : nullptr;      // layers >= 1 read x = (v2c w_in + b_in) + F_{l-1}
         L.x_out = (l % 2 == 0) ? w.xa : w.xb;  // F
         launch(proj_k, B * (int64_t)(T.n_tiles - T.first), cus, s, L, T);
         LDPC_CHECK_LAUNCH("gnn_group_proj_kernel (check side)");
         launch(mlp_k, (R + 31) / 32, cus, s, L);
         LDPC_CHECK_LAUNCH("gnn_mlp2_kernel (check side)");
         hipLaunchKernelGGL(custom_var_llr_kernel, dim3((unsigned)((B * N + 255) / 256)), dim3(256), 0, s, w.msg_out, w.csr,
-                           d_llr, p->E, N, B, v2c);
+                           d_llr, p->E, N, B, w.v2c);
         LDPC_CHECK_LAUNCH("hybrid GNN variable update");
         if (l == layers - 1)  // x_L and the decoder's output head, the last layer's (:855)
             hipLaunchKernelGGL(custom_combine_kernel, dim3((unsigned)((R * 16 + 255) / 256)), dim3(256), 0, s, L.x_out,
-                               v2c, d_weights, d_weights + H, R, L.wo, L.bo, w.msg_out);
+                               w.v2c, d_weights, d_weights + H, R, L.wo, L.bo, w.msg_out);
         LDPC_CHECK_LAUNCH("hybrid GNN output head");
         L.x_in = L.x_out;
     }

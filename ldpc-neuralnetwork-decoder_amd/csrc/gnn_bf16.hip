@@ -699,32 +699,29 @@ struct Bf16Ws {
     int64_t bytes;
 };
 
+// The bf16 forward's buffers, taken in the order they lie in the workspace
 Bf16Ws carve_bf16(const ldpc_gnn_plan *p, int N, int64_t B, int T, int L, void *base) {
-    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
-    const int64_t kd = al(L * kd_floats(T) * 4), memb = al((int64_t)L * (p->Gv + p->Gc) * H * 4) * 3 / 2;
-    const int64_t xa = L > 1 ? al(B * p->E * H * 2) : 0, xb = L > 2 ? xa : 0;
-    const int64_t mv = al(B * p->Gv * H * 2), mc = al(B * p->Gc * H * 2), vs = al(B * p->E * 4);
-    const int64_t nslot = (int64_t)p->n_ctiles * 32;
-    const int64_t inf = al(nslot * 16) + al(nslot * 8), act = al(B), cs = al(gnn_csr_ints(p->E, N) * 4);
-    const int64_t alb = al(2 * B * 4) + 256;  // two active lists [B] + the two ranges' two counts
-    char *c = static_cast<char *>(base);
     Bf16Ws w;
-    w.info = reinterpret_cast<int4 *>(c + kd + memb + xa + xb + mv + mc + vs);
-    w.slot = reinterpret_cast<int2 *>(c + kd + memb + xa + xb + mv + mc + vs + al(nslot * 16));
-    w.active = reinterpret_cast<uint8_t *>(c + kd + memb + xa + xb + mv + mc + vs + inf);
-    w.csr = reinterpret_cast<int32_t *>(c + kd + memb + xa + xb + mv + mc + vs + inf + act);
-    w.kd = reinterpret_cast<float *>(c);
-    w.memb = reinterpret_cast<float *>(c + kd);
-    w.memb16 = reinterpret_cast<__bf16 *>(c + kd + al((int64_t)L * (p->Gv + p->Gc) * H * 4));
-    w.xa = reinterpret_cast<__bf16 *>(c + kd + memb);
-    w.xb = reinterpret_cast<__bf16 *>(c + kd + memb + xa);
-    w.Mv = reinterpret_cast<__bf16 *>(c + kd + memb + xa + xb);
-    w.Mc = reinterpret_cast<__bf16 *>(c + kd + memb + xa + xb + mv);
-    w.msg_out = reinterpret_cast<float *>(c + kd + memb + xa + xb + mv + mc);
-    w.alist = reinterpret_cast<int32_t *>(c + kd + memb + xa + xb + mv + mc + vs + inf + act + cs);
-    w.acount = reinterpret_cast<int32_t *>(c + kd + memb + xa + xb + mv + mc + vs + inf + act + cs + al(2 * B * 4));
-    w.cg_var = reinterpret_cast<int32_t *>(c + kd + memb + xa + xb + mv + mc + vs + inf + act + cs + alb);
-    w.bytes = kd + memb + xa + xb + mv + mc + vs + inf + act + cs + alb + al(p->E * 4);
+    GnnArena a(base);
+    const int64_t memb = (int64_t)L * (p->Gv + p->Gc) * H * 4, x = B * p->E * H * 2;
+    const int64_t nslot = (int64_t)p->n_ctiles * 32;
+    w.kd = a.take<float>(L * kd_floats(T) * 4);
+    w.memb = a.take<float>(memb);
+    // the bf16 copy is half of a multiple of 256 B: what follows is 128-B aligned when L (Gv + Gc) is odd
+    w.memb16 = a.take<__bf16>(memb / 2, 128);
+    w.xa = a.take<__bf16>(L > 1 ? x : 0);  // a feature buffer no layer writes takes no bytes
+    w.xb = a.take<__bf16>(L > 2 ? x : 0);
+    w.Mv = a.take<__bf16>(B * p->Gv * H * 2);
+    w.Mc = a.take<__bf16>(B * p->Gc * H * 2);
+    w.msg_out = a.take<float>(B * p->E * 4);
+    w.info = a.take<int4>(nslot * 16);
+    w.slot = a.take<int2>(nslot * 8);
+    w.active = a.take<uint8_t>(B);
+    w.csr = a.take<int32_t>(gnn_csr_ints(p->E, N) * 4);
+    w.alist = a.take<int32_t>(2 * B * 4);  // two active lists [B]
+    w.acount = a.take<int32_t>(256);       // the two ranges' two counts
+    w.cg_var = a.take<int32_t>(p->E * 4);
+    w.bytes = a.bytes;
     return w;
 }
 

@@ -1660,12 +1660,10 @@ struct TrainWs {
 };
 
 TrainWs carve_train(const ldpc_gnn_plan *p, int H, int N, int64_t B, void *base) {
-    auto al = [](int64_t x) { return (x + 63) / 64 * 64; };  // floats (256-B alignment)
-    const int64_t reh = al(B * p->E * H), mv = al(B * p->Gv * H), mc = al(B * p->Gc * H), nz = al(B * N);
-    float *c = static_cast<float *>(base);
+    const int64_t reh = B * p->E * H, mv = B * p->Gv * H, mc = B * p->Gc * H, nz = B * N;  // floats
     TrainWs w;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { float *q = c + o; o += n; return q; };
+    GnnArena a(base);
+    auto take = [&](int64_t n) { return a.take<float>(n * 4); };
     w.Mv = take(mv);
     w.Mc = take(mc);
     w.Mda = take(mv);
@@ -1685,7 +1683,7 @@ TrainWs carve_train(const ldpc_gnn_plan *p, int H, int N, int64_t B, void *base)
     w.Mc1 = take(mc);
     w.Gs1v = take(mv);
     w.Gs1c = take(mc);
-    w.bytes = o * 4;
+    w.bytes = a.bytes;
     return w;
 }
 

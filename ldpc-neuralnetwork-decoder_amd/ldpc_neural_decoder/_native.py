@@ -50,6 +50,8 @@ SIGNATURES = {
     "ldpc_gnn_plan_create": (ctypes.c_int, [_I64, ctypes.c_int, _P, ctypes.c_int, _P, _P]),
     "ldpc_gnn_plan_create_csr": (ctypes.c_int, [_I64, _P, _P, _P, _P, _P, _P, _P]),
     "ldpc_gnn_plan_destroy": (ctypes.c_int, [_P]),
+    "ldpc_gnn_plan_tables": (_I64, [_I64, ctypes.c_int, _P, ctypes.c_int, _P, _P, _I64]),
+    "ldpc_gnn_plan_tables_csr": (_I64, [_I64, _P, _P, _P, _P, _P, _P, _P, _I64]),
     "ldpc_gnn_weights_size": (_I64, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "ldpc_gnn_workspace_size": (_I64, [_P, ctypes.c_int, ctypes.c_int, _I64, ctypes.c_int, ctypes.c_int]),
     "ldpc_gnn_forward": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,

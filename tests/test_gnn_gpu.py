@@ -183,3 +183,39 @@ def test_fp32_group_mean_variants_bit_identical(cuda, tmp_path):
     d = (p - child("norw.pt", LDPC_GNN_ROWWALK="0")).abs().max().item()
     print(f"row walk vs tile walk: max |dp| {d:.2e}")
     assert d <= 1e-5
+
+
+# (hidden, layers) -> for B = 0, 1, 5: [ldpc_gnn_workspace_size precision 0, precision 1,
+# ldpc_gnn_train_workspace_size, ldpc_gnn_custom_var_workspace_size] on the BG2 Z = 4 plan.  Recorded
+# on an MI355X from the library of the commit before the workspaces moved onto GnnArena (built from a
+# clean export and selected with LDPC_AMD_LIB, as tools/gpu_ab.sh does).
+_WORKSPACE_BYTES = {
+    (32, 1): [[29440, 327936, 29440, 78592], [80896, 379904, 1202176, 335104], [285952, 584960, 6010112, 1359616]],
+    (32, 2): [[54016, 627456, 54016, 78592], [206336, 780288, 1202176, 335104], [814848, 1388800, 6010112, 1359616]],
+    (32, 3): [[78592, 926976, 78592, 78592], [331776, 1180672, 1202176, 335104], [1343744, 2192640, 6010112, 1359616]],
+    (64, 1): [[4864, 327936, 4864, 4864], [104448, 379904, 2403328, 511232], [502016, 584960, 12015872, 2535168]],
+    (64, 2): [[4864, 627456, 4864, 4864], [306176, 780288, 2403328, 511232], [1510656, 1388800, 12015872, 2535168]],
+    (64, 3): [[4864, 926976, 4864, 4864], [507904, 1180672, 2403328, 511232], [2519296, 2192640, 12015872, 2535168]],
+    (96, 1): [[346112, 327936, 226048, 668416], [1557760, 379904, 3604480, 1424640], [6400256, 584960, 18021632, 4448000]],
+    (96, 2): [[687104, 627456, 447232, 668416], [2201344, 780288, 3604480, 1424640], [8254208, 1388800, 18021632, 4448000]],
+    (96, 3): [[1028096, 926976, 668416, 668416], [2542336, 1180672, 3604480, 1424640], [8595200, 2192640, 18021632, 4448000]],
+    (128, 1): [[525312, 327936, 398080, 1184512], [2135808, 379904, 4805632, 2190592], [8573696, 584960, 24027392, 6213376]],
+    (128, 2): [[1045504, 627456, 791296, 1184512], [3059456, 780288, 4805632, 2190592], [11111168, 1388800, 24027392, 6213376]],
+    (128, 3): [[1565696, 926976, 1184512, 1184512], [3579648, 1180672, 4805632, 2190592], [11631360, 2192640, 24027392, 6213376]],
+}
+
+
+def test_workspace_totals_are_pinned(cuda):
+    """Every workspace is carved from one arena, its buffers taken in the order they lie; with that
+    order, equal totals and the bitwise GNN tests are the check that no offset moved."""
+    from ldpc_neural_decoder import _native as N
+    from ldpc_neural_decoder.models.message_gnn_decoder import TannerToMessageGraph
+    conv = TannerToMessageGraph(expand_base_matrix(load_base_matrix(code_path(4)), 4))
+    plan = N.NativeGnnPlan(*conv.var_groups, *conv.check_groups, cuda)
+    lib, nv = N.lib(), conv.num_variables
+    got = {(H, L): [[lib.ldpc_gnn_workspace_size(plan.handle, H, nv, B, L, 0),
+                     lib.ldpc_gnn_workspace_size(plan.handle, H, nv, B, L, 1),
+                     lib.ldpc_gnn_train_workspace_size(plan.handle, H, nv, B, L),
+                     lib.ldpc_gnn_custom_var_workspace_size(plan.handle, H, nv, B, L)] for B in (0, 1, 5)]
+           for H in (32, 64, 96, 128) for L in (1, 2, 3)}
+    assert got == _WORKSPACE_BYTES
