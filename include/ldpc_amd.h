@@ -194,9 +194,10 @@ int ldpc_count_errors(const void *d_bits, int bits_dtype, const uint8_t *d_ref, 
  * d_probs (B, N) float32 = sigmoid(llr + sum of each variable's projected messages).
  * d_work: at least ldpc_gnn_workspace_size(plan, H, N, B, precision) bytes. */
 typedef struct ldpc_gnn_plan ldpc_gnn_plan;
-/* ldpc_gnn_forward_ex flags */
+/* flags of ldpc_gnn_forward_ex (and, FP32_PRODUCTS, of the training and hybrid _ex entries) */
 #define LDPC_GNN_EARLY_STOP 1 /* cfg5 per-frame early termination (bf16 path; see below) */
 #define LDPC_GNN_FP32_PRODUCTS 2 /* fp32 path, H = 64: every product on the fp32 MFMA (see below) */
+#define LDPC_GNN_CHECK_RANGE 4   /* training forward: decide FP32_PRODUCTS from the weights, on the device */
 int ldpc_gnn_plan_create(int64_t E, int n_vgroups, const int32_t *h_vgroup, int n_cgroups,
                          const int32_t *h_cgroup, ldpc_gnn_plan **out);
 /* General adjacencies: the reference runs a dense bmm with whatever (E x E) matrices it is given
@@ -236,7 +237,23 @@ int ldpc_gnn_custom_var_forward(const ldpc_gnn_plan *p, int hidden, int types, i
                                 const float *d_weights, const int32_t *d_msg_type,
                                 const int32_t *d_msg_var, const float *d_llr, int N, int64_t B,
                                 float *d_probs, void *d_work, int64_t work_bytes, void *stream);
+/* ldpc_gnn_custom_var_forward_ex: ... plus flags.  LDPC_GNN_FP32_PRODUCTS (hidden 64): the check side's
+ * products on the fp32 MFMA instead of as f16 splits, for weights beyond the splits' range (see
+ * ldpc_gnn_forward_ex); other widths run fp32 fma chains either way. */
+int ldpc_gnn_custom_var_forward_ex(const ldpc_gnn_plan *p, int hidden, int types, int layers,
+                                   const float *d_weights, const int32_t *d_msg_type,
+                                   const int32_t *d_msg_var, const float *d_llr, int N, int64_t B, int flags,
+                                   float *d_probs, void *d_work, int64_t work_bytes, void *stream);
 int64_t ldpc_gnn_weights_size(int hidden, int types, int layers);
+/* Whether a weight blob is beyond the f16 splits' range: *d_exceeded (device int32) = 1 when, in some
+ * layer, a nonzero row of a weight group has its largest |w| below `range` (2^-17) times the group's
+ * largest, else 0.  The groups are those that share one power-of-two scale: hidden 64, the projection's
+ * W1v / W1c right halves, and the MLP's left halves, W2v, W2c and W1v_left + W1v_right; hidden 96..256,
+ * each side's W1 right half, both left halves together, and W2v | W2c row by row.  Other widths have no
+ * splits (always 0).  One launch, no synchronisation.  (The training forward asks the same question
+ * itself under LDPC_GNN_CHECK_RANGE.) */
+int ldpc_gnn_split_range_exceeded(int hidden, int types, int layers, const float *d_weights, float range,
+                                  int32_t *d_exceeded, void *stream);
 int64_t ldpc_gnn_workspace_size(const ldpc_gnn_plan *p, int hidden, int N, int64_t B, int layers,
                                 int precision);
 int ldpc_gnn_forward(const ldpc_gnn_plan *p, int hidden, int types, int layers,
@@ -316,6 +333,27 @@ int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int types, int l
                             int64_t B, const float *d_probs, const float *d_grad_probs, const float *d_saved,
                             const float *d_proj, const float *d_layer_probs, const float *d_grad_layer_probs,
                             float *d_grad_weights, void *d_work, int64_t work_bytes, void *stream);
+/* ldpc_gnn_forward_train_ex2 / ldpc_gnn_backward_ds_ex2: the _ex functions plus flags.
+ *   LDPC_GNN_FP32_PRODUCTS (hidden 64, group plans): the training forward's products of W1_right g and of
+ *   the MLP on the fp32 MFMA instead of as f16 splits, as ldpc_gnn_forward_ex does for inference, and
+ *   the projections the backward recomputes (d_proj null) likewise; the backward's own MLP products are
+ *   three-term bf16 splits or fp32 MFMAs, which hold fp32's range.  Other widths train on fp32 fma chains
+ *   and ignore the flag.
+ *   LDPC_GNN_CHECK_RANGE (forward): the forward itself decides FP32_PRODUCTS, by the rule of
+ *   ldpc_gnn_split_range_exceeded with range 2^-17, for a trainer whose weights are new at every step.  It
+ *   queues the check and its preparation, synchronises the stream once, and launches the layers; a stream
+ *   under capture cannot take this flag.
+ *   *flags_used (host, optional) receives the flags the forward ran with (FP32_PRODUCTS or 0): pass them
+ *   to ldpc_gnn_backward_ds_ex2. */
+int ldpc_gnn_forward_train_ex2(const ldpc_gnn_plan *p, int hidden, int types, int layers,
+                               const float *d_weights, const int32_t *d_msg_type, const int32_t *d_msg_var,
+                               const float *d_llr, int N, int64_t B, float *d_probs, float *d_saved, float *d_proj,
+                               int flags, int *flags_used, void *d_work, int64_t work_bytes, void *stream);
+int ldpc_gnn_backward_ds_ex2(const ldpc_gnn_plan *p, int hidden, int types, int layers, const float *d_weights,
+                             const int32_t *d_msg_type, const int32_t *d_msg_var, const float *d_llr, int N,
+                             int64_t B, const float *d_probs, const float *d_grad_probs, const float *d_saved,
+                             const float *d_proj, const float *d_layer_probs, const float *d_grad_layer_probs,
+                             float *d_grad_weights, int flags, void *d_work, int64_t work_bytes, void *stream);
 
 /* ---- index-gather neural-BP layers (models/layers.py) ------------------
  * d_idx is the reference's (n_out, K) index tensor transposed to (K, n_out) int32, -1 = padding

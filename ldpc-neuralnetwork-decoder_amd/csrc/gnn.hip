@@ -1018,6 +1018,10 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
 
     const int lane = tid & 63, j = lane & 31, half = lane >> 5, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform: the walk's indices in SGPRs
     const float bo = P.last ? P.bo[0] : 0.0f;
+    // the largest |output bias| (uniform): with a message's largest |x| it bounds y's seed (seed_exp_cap)
+    float b2m = 0.0f;
+    for (int u = 0; u < 64; ++u) b2m = fmaxf(b2m, fabsf(lds[kS6OffB + u]));
+    b2m = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(b2m)));
     // A fragment of row j (+ 32 kS6Row: rows 32 .., whose swizzle equals row j's), k-step s
     auto aof = [&](int s) { return s6_at(j, 16 * s + 8 * half); };
     const bool vs = HYB ? P.vside != 0 : true;  // the var side (only the hybrid kernel runs without it)
@@ -1104,7 +1108,11 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
         for (int s = 0; s < 4; ++s)
 #pragma unroll
             for (int i = 0; i < 8; ++i) cm = fmaxf(cm, fabsf(x[s][i]));
-        cm = fmaxf(cm, __shfl_xor(cm, 32, 64)) + lds[kS6OffEmb + P.T * kPS + typ];  // >= max |c|
+        cm = fmaxf(cm, __shfl_xor(cm, 32, 64));  // max |x|
+        // GEMM2's accumulators are seeded with b2 (+ x) and scaled with relu(h)'s column: the scale is
+        // capped where it would carry that seed past fp32's range
+        const int ycap = seed_exp_cap((P.residual ? cm : 0.0f) + b2m, wexp);
+        cm += lds[kS6OffEmb + P.T * kPS + typ];  // >= max |c|
         const int cexp = col_exp_w(cm, wexp);
         const float csc = pow2f(cexp), asc = pow2f(cexp + wexp), iasc = pow2f(-cexp - wexp);
         hs[0][0] *= asc;
@@ -1160,7 +1168,7 @@ __global__ __launch_bounds__(NT, WPS) void gnn_mlp2s_kernel(GnnLayer P) {
             for (int r = 0; r < 16; ++r) hm = fmaxf(hm, fmaxf(hs[side][0][r], hs[side][1][r]));
         }
         hm = fmaxf(hm, __shfl_xor(hm, 32, 64));  // >= 0: the largest relu(h)
-        const int hexp = col_exp_w(hm, wexp);
+        const int hexp = min(col_exp_w(hm, wexp), ycap);
         const float hsc = pow2f(hexp), ysc = pow2f(hexp + wexp), iysc = pow2f(-hexp - wexp);
         y0 *= ysc;
         y1 *= ysc;
@@ -1901,7 +1909,7 @@ void launch(const Kernel<A...> &k, int64_t units, int cus, hipStream_t s, A... a
 ProjKernel select_proj(int types, bool hyb, bool f16, bool gen) {
     const bool big = !hyb && proj_lds_bytes(types, kProjNt / 64) <= kLdsMax;
     ProjKernel k{};
-    k.fn = hyb    ? gnn_group_proj_kernel<256, true>
+    k.fn = hyb    ? (f16 ? gnn_group_proj_kernel<256, true> : gnn_group_proj_kernel<256, true, false>)
            : !f16 ? (big ? gnn_group_proj_kernel<kProjNt, false, false> : gnn_group_proj_kernel<256, false, false>)
            : !gen ? (big ? gnn_group_proj_kernel<kProjNt, false, true, false> : gnn_group_proj_kernel<256, false, true, false>)
                   : (big ? gnn_group_proj_kernel<kProjNt> : gnn_group_proj_kernel<256>);
@@ -1944,6 +1952,69 @@ int launch_tiled(const GnnLayer &L, int H, int64_t R, int cus, hipStream_t s, co
     LDPC_CHECK_LAUNCH(what);
     return LDPC_OK;
 }
+// ---- the f16 splits' weight range, checked on the device (training: the weights change every step,
+// and the host-side check of MessageGNNDecoder._split_range_ok costs a synchronisation per weight
+// group).  The groups are the ones stated there: a group's rows share one power-of-two scale, and
+// a row keeps 22 bits while its largest |w| is at least `range` of the group's.  One workgroup per
+// (layer, group); *exceeded (zeroed by the caller) becomes 1 when some nonzero row falls below.
+constexpr float kSplitRange = 0x1p-17f;  // = MessageGNNDecoder.SPLIT_RANGE
+struct RangeSet {
+    const float *a, *b;  // rows of a; b: null, or summed to a elementwise (op 1), or its row beside a's (op 2)
+    int stride, op;
+};
+__global__ __launch_bounds__(256) void gnn_split_range_kernel(const float *blob, int H, int T, int wide, float range,
+                                                              int32_t *exceeded) {
+    const int ngroups = wide ? 4 : 2;
+    const int l = blockIdx.x / ngroups, g = blockIdx.x % ngroups;
+    const auto w = gnn_layer_weights(blob, H, T, l);
+    const RangeSet w1vL{w.w1v, nullptr, 2 * H, 0}, w1vR{w.w1v + H, nullptr, 2 * H, 0};
+    const RangeSet w1cL{w.w1c, nullptr, 2 * H, 0}, w1cR{w.w1c + H, nullptr, 2 * H, 0};
+    RangeSet set[5];
+    int n = 0;
+    if (!wide) {  // H = 64: the projection's group, then the MLP's (with the degree-1 image W1v_left + W1v_right)
+        if (g == 0) {
+            set[n++] = w1vR; set[n++] = w1cR;
+        } else {
+            set[n++] = w1vL; set[n++] = w1cL;
+            set[n++] = {w.w2v, nullptr, H, 0}; set[n++] = {w.w2c, nullptr, H, 0};
+            set[n++] = {w.w1v, w.w1v + H, 2 * H, 1};
+        }
+    } else if (g < 2) {  // H = 96 .. 256: each side's projection, both W1 left halves, W2v | W2c
+        set[n++] = g ? w1cR : w1vR;
+    } else if (g == 2) {
+        set[n++] = w1vL; set[n++] = w1cL;
+    } else {
+        set[n++] = {w.w2v, w.w2c, H, 2};
+    }
+    __shared__ int lo, hi;  // float bits: positive floats order as their bits
+    if (threadIdx.x == 0) {
+        lo = 0x7f800000;
+        hi = 0;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = 0; k < n; ++k) {
+        const RangeSet q = set[k];
+        for (int r = wave; r < H; r += 4) {  // one wave per row
+            float m = 0.0f;
+            for (int c = lane; c < H; c += 64) {
+                float v = q.a[(int64_t)r * q.stride + c];
+                if (q.op == 1) v += q.b[(int64_t)r * q.stride + c];
+                m = fmaxf(m, fabsf(v));
+                if (q.op == 2) m = fmaxf(m, fabsf(q.b[(int64_t)r * q.stride + c]));
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+            if (lane == 0) {
+                atomicMax(&hi, __float_as_int(m));
+                if (m > 0.0f) atomicMin(&lo, __float_as_int(m));
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && hi > 0 && __int_as_float(lo) < __int_as_float(hi) * range) *exceeded = 1;
+}
+
 // the split MLP (default) unless LDPC_GNN_SPLIT=0, fp32 products are asked for or the type table is too long
 bool split_on(int types, bool fp32_products) {
     return !fp32_products && split_path() && mlp2s_lds_bytes(types, false) <= kLdsMax;
@@ -2033,6 +2104,26 @@ int ldpc::gnn_side_stream(hipStream_t *side, hipEvent_t *fork, hipEvent_t *join)
     return LDPC_OK;
 }
 
+// One pinned host word per device and calling thread that kernels write through its device address
+// (coherent host memory): the range check's answer, read after a stream synchronise with no copy.
+int ldpc::gnn_range_word(int32_t **host, int32_t **dev) {
+    constexpr int kMaxDev = 64;
+    thread_local int32_t *words[kMaxDev], *dwords[kMaxDev];
+    int d = 0;
+    LDPC_HIP(hipGetDevice(&d));
+    if (d < 0 || d >= kMaxDev) return fail(LDPC_EUNSUPPORTED, "device index out of range");
+    if (!words[d]) {
+        void *h = nullptr, *dp = nullptr;
+        LDPC_HIP(hipHostMalloc(&h, sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
+        LDPC_HIP(hipHostGetDevicePointer(&dp, h, 0));
+        words[d] = static_cast<int32_t *>(h);
+        dwords[d] = static_cast<int32_t *>(dp);
+    }
+    *host = words[d];
+    *dev = dwords[d];
+    return LDPC_OK;
+}
+
 using namespace ldpc;
 
 int ldpc::gnn_build_var_csr(const int32_t *d_msg_var, int64_t E, int N, int32_t *d_ints, hipStream_t s) {
@@ -2068,6 +2159,20 @@ extern "C" int64_t ldpc_gnn_weights_size(int hidden, int types, int layers) {
     return 2LL * hidden + (int64_t)layers * gnn_layer_floats(hidden, types);
 }
 
+extern "C" int ldpc_gnn_split_range_exceeded(int hidden, int types, int layers, const float *d_weights, float range,
+                                             int32_t *d_exceeded, void *stream) {
+    if (hidden <= 0 || types <= 0 || layers <= 0) return fail(LDPC_EINVAL, "bad GNN dimensions");
+    if (!d_weights || !d_exceeded) return fail(LDPC_EINVAL, "NULL tensor");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LDPC_HIP(hipMemsetAsync(d_exceeded, 0, sizeof(int32_t), s));
+    const bool wide = gnn_wide_supported(hidden);
+    if (hidden != kMfmaH && !wide) return LDPC_OK;  // fp32 fma chains: no splits
+    hipLaunchKernelGGL(gnn_split_range_kernel, dim3((unsigned)(layers * (wide ? 4 : 2))), dim3(256), 0, s, d_weights, hidden,
+                       types, wide ? 1 : 0, range, d_exceeded);
+    LDPC_CHECK_LAUNCH("gnn_split_range_kernel");
+    return LDPC_OK;
+}
+
 extern "C" int64_t ldpc_gnn_workspace_size(const ldpc_gnn_plan *p, int hidden, int N, int64_t B, int layers,
                                            int precision) {
     if (!p || hidden <= 0 || N <= 0 || B < 0 || layers <= 0) return fail(LDPC_EINVAL, "bad arguments");
@@ -2088,7 +2193,7 @@ int64_t ldpc::gnn_proj_floats(const ldpc_gnn_plan *p, int hidden, int64_t B, int
 int ldpc::gnn_fp32_forward(const ldpc_gnn_plan *p, int hidden, int types, int layers, const float *d_weights,
                            const int32_t *d_msg_type, const int32_t *d_msg_var, const float *d_llr, int N, int64_t B,
                            float *d_probs, float *d_saved, void *d_work, int64_t work_bytes, hipStream_t s,
-                           float *d_proj, bool fp32_products) {
+                           float *d_proj, bool fp32_products, bool check_range, bool *ran_fp32) {
     const int H = hidden;
     const bool train = d_saved != nullptr;
     Ws w = carve(p, H, N, B, layers, d_work, train);
@@ -2098,14 +2203,35 @@ int ldpc::gnn_fp32_forward(const ldpc_gnn_plan *p, int hidden, int types, int la
     if (int rc = gnn_num_cus(&cus)) return rc;
     if (int rc = gnn_build_var_csr(d_msg_var, p->E, N, w.csr, s)) return rc;
     if (H != kMfmaH && H > kMaxGenericH) return fail(LDPC_EUNSUPPORTED, "hidden_dim must be <= " + std::to_string(kMaxGenericH));
-    const Fp32Path f = fp32_path(p, H, types, train, fp32_products, w.S != nullptr, w.wimg != nullptr);
-    if (f.too_many_types) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
-    if (f.mfma) LDPC_HIP(raise_lds(f.mfma_k));
-    if (f.proj) {
-        LDPC_HIP(raise_lds(f.proj_k));
-        LDPC_HIP(raise_lds(f.proj_rw_k));
-        LDPC_HIP(raise_lds(f.mlp_k));
+    // check_range (H = 64, whose kernels run the f16 splits): the weights' range is decided on the device
+    // and read back once, after everything that does not depend on it is queued -- the host then waits
+    // for the stream with only the layers left to launch.  A caller that has decided passes fp32_products.
+    const bool decide = check_range && !fp32_products && H == kMfmaH;
+    volatile int32_t *range_word = nullptr;
+    if (decide) {
+        int32_t *h = nullptr, *d = nullptr;
+        if (int rc = gnn_range_word(&h, &d)) return rc;
+        *h = 0;
+        hipLaunchKernelGGL(gnn_split_range_kernel, dim3((unsigned)(layers * 2)), dim3(256), 0, s, d_weights, H, types, 0,
+                           kSplitRange, d);
+        LDPC_CHECK_LAUNCH("gnn_split_range_kernel");
+        range_word = h;
     }
+    auto path_of = [&](bool fp32p) { return fp32_path(p, H, types, train, fp32p, w.S != nullptr, w.wimg != nullptr); };
+    auto prepare = [&](const Fp32Path &f) -> int {
+        if (f.too_many_types) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
+        if (f.mfma) LDPC_HIP(raise_lds(f.mfma_k));
+        if (f.proj) {
+            LDPC_HIP(raise_lds(f.proj_k));
+            LDPC_HIP(raise_lds(f.proj_rw_k));
+            LDPC_HIP(raise_lds(f.mlp_k));
+        }
+        return LDPC_OK;
+    };
+    Fp32Path f = path_of(fp32_products);
+    if (int rc = prepare(f)) return rc;
+    if (decide)
+        if (int rc = prepare(path_of(true))) return rc;
     // per-call preparation, on the caller's stream before the frame halves fork
     const float *emb0 = gnn_layer_weights(d_weights, H, types, 0).emb;
     if (f.proj && f.rw) {  // every layer's mean type embedding per check group and per var group
@@ -2132,6 +2258,14 @@ int ldpc::gnn_fp32_forward(const ldpc_gnn_plan *p, int hidden, int types, int la
         }
     }
     const GnnLayer L0 = plan_layer(p, H, types, d_weights, d_msg_type, d_msg_var, d_llr, N, B, w.Mv, w.Mc);
+    if (decide) {
+        LDPC_HIP(hipStreamSynchronize(s));
+        if (*range_word) {
+            fp32_products = true;
+            f = path_of(true);
+        }
+    }
+    if (ran_fp32) *ran_fp32 = fp32_products;
     // frames [b0, b0 + nb) through every layer on stream st (pointers offset to the range)
     auto run_range = [&](int64_t b0, int64_t nb, hipStream_t st) -> int {
         GnnLayer L = L0;
@@ -2264,7 +2398,8 @@ int ldpc::gnn_fp32_forward(const ldpc_gnn_plan *p, int hidden, int types, int la
 
 int ldpc::gnn_project_groups(const ldpc_gnn_plan *p, int types, const float *d_weights, int layer, const float *d_x,
                              const int32_t *d_msg_type, const int32_t *d_msg_var, const float *d_llr, int N,
-                             int64_t B, float *d_pv, float *d_pc, float *d_gv, float *d_gc, hipStream_t s) {
+                             int64_t B, float *d_pv, float *d_pc, float *d_gv, float *d_gc, hipStream_t s,
+                             bool fp32_products) {
     constexpr int H = kMfmaH;
     if (p->weighted || p->n_ptiles <= 0) return fail(LDPC_EUNSUPPORTED, "group projection needs a group plan");
     int cus = 0;
@@ -2273,7 +2408,7 @@ int ldpc::gnn_project_groups(const ldpc_gnn_plan *p, int types, const float *d_w
     L.x_in = d_x;
     L.gsave_v = d_gv; L.gsave_c = d_gc;
     set_layer_weights(L, gnn_layer_weights(d_weights, H, types, layer));
-    const ProjKernel k = select_proj(types, false, true, true);
+    const ProjKernel k = select_proj(types, false, !fp32_products, true);
     if (!k.fits()) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
     LDPC_HIP(raise_lds(k));
     const ProjTiles T{p->pt_meta, p->pt_grp, p->pt_deg, p->pt_mem, p->n_ptiles, 0};
@@ -2382,7 +2517,18 @@ extern "C" int ldpc_gnn_custom_var_forward(const ldpc_gnn_plan *p, int hidden, i
                                            const float *d_weights, const int32_t *d_msg_type,
                                            const int32_t *d_msg_var, const float *d_llr, int N, int64_t B,
                                            float *d_probs, void *d_work, int64_t work_bytes, void *stream) {
+    return ldpc_gnn_custom_var_forward_ex(p, hidden, types, layers, d_weights, d_msg_type, d_msg_var, d_llr, N, B, 0,
+                                          d_probs, d_work, work_bytes, stream);
+}
+
+extern "C" int ldpc_gnn_custom_var_forward_ex(const ldpc_gnn_plan *p, int hidden, int types, int layers,
+                                              const float *d_weights, const int32_t *d_msg_type,
+                                              const int32_t *d_msg_var, const float *d_llr, int N, int64_t B,
+                                              int flags, float *d_probs, void *d_work, int64_t work_bytes,
+                                              void *stream) {
     if (!p) return fail(LDPC_EINVAL, "plan is NULL");
+    if (flags & ~LDPC_GNN_FP32_PRODUCTS) return fail(LDPC_EINVAL, "unknown flags");
+    const bool fp32_products = (flags & LDPC_GNN_FP32_PRODUCTS) != 0;  // H = 64 (other widths: fp32 fma chains)
     if (hidden <= 0 || hidden > kTiledMaxH) return fail(LDPC_EUNSUPPORTED, "the hybrid GNN runs at hidden_dim <= 1024");
     if (p->weighted || p->n_ptiles == 0) return fail(LDPC_EUNSUPPORTED, "the hybrid GNN needs a group plan");
     if (types <= 0 || layers <= 0 || N <= 0 || B < 0) return fail(LDPC_EINVAL, "bad dimensions");
@@ -2399,8 +2545,8 @@ extern "C" int ldpc_gnn_custom_var_forward(const ldpc_gnn_plan *p, int hidden, i
     const Ws w = carve_hybrid(p, H, N, B, layers, d_work);
     int cus = 0;
     if (int rc = gnn_num_cus(&cus)) return rc;
-    const ProjKernel proj_k = select_proj(types, true, true, true);
-    const MlpKernel mlp_k = select_mlp(types, true, split_on(types, false), false, false, false);
+    const ProjKernel proj_k = select_proj(types, true, !fp32_products, true);
+    const MlpKernel mlp_k = select_mlp(types, true, split_on(types, fp32_products), false, false, false);
     if (!proj_k.fits() || !mlp_k.fits()) return fail(LDPC_EUNSUPPORTED, "too many message types for the LDS image");
     LDPC_HIP(raise_lds(proj_k));
     LDPC_HIP(raise_lds(mlp_k));

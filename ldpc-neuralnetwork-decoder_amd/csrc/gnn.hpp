@@ -148,17 +148,22 @@ __device__ __forceinline__ const int32_t *csr_mem(const int32_t *ints, int N) { 
 int gnn_fp32_forward(const ldpc_gnn_plan *p, int hidden, int types, int layers, const float *d_weights,
                      const int32_t *d_msg_type, const int32_t *d_msg_var, const float *d_llr, int N, int64_t B,
                      float *d_probs, float *d_saved, void *d_work, int64_t work_bytes, hipStream_t s,
-                     float *d_proj = nullptr, bool fp32_products = false);
+                     float *d_proj = nullptr, bool fp32_products = false, bool check_range = false,
+                     bool *ran_fp32 = nullptr);
+// check_range: decide fp32_products from the weights on the device (gnn_split_range_kernel; one stream
+// synchronise, after the call's preparation is queued); ran_fp32 receives what the layers ran with
+int gnn_range_word(int32_t **host, int32_t **dev);
 int64_t gnn_proj_floats(const ldpc_gnn_plan *p, int hidden, int64_t B, int layers);
 // workspace of the training forward (gnn_fp32_forward with d_saved: never the wide path)
 int64_t gnn_fp32_train_workspace(const ldpc_gnn_plan *p, int hidden, int N, int64_t B, int layers);
 
 // Layer `layer`'s projected group rows W1_s,right g + b1_s (d_pv / d_pc, (B, G, 64)) and, when
 // d_gv is set, the group means g themselves (d_gv / d_gc) of c = x + emb (x = d_x, or the LLR
-// embedding when d_x is null): the fp32 forward's projection kernel, for the training backward.
+// embedding when d_x is null): the fp32 forward's projection kernel (its fp32-MFMA instance with
+// fp32_products), for the training backward.
 int gnn_project_groups(const ldpc_gnn_plan *p, int types, const float *d_weights, int layer, const float *d_x,
                        const int32_t *d_msg_type, const int32_t *d_msg_var, const float *d_llr, int N, int64_t B,
-                       float *d_pv, float *d_pc, float *d_gv, float *d_gc, hipStream_t s);
+                       float *d_pv, float *d_pc, float *d_gv, float *d_gc, hipStream_t s, bool fp32_products = false);
 
 // fp32 layer at hidden widths H = 32 k other than 64 (gnn_wide.hip): row GEMMs on the bf16 MFMA with
 // three-term splits.  Pointers are offset to the frame range [0, B); y = the layer's output rows
@@ -313,6 +318,15 @@ __device__ __forceinline__ int col_exp(float m) {
 // column's own scale 2^e a normal float too (pow2f exact) when the weights' exponent is far from 0.
 __device__ __forceinline__ int col_exp_w(float m, int wexp) {
     return min(max(min(max(col_exp(m), -126 - wexp), 126 - wexp), -126), 127);
+}
+// The largest column exponent e under which accumulators seeded with values of magnitude <= m (the
+// output biases and the residual) stay finite once scaled by 2^(e + wexp): m < 2^(b - 126) for its
+// biased exponent b, so the scaled seed stays below 2^124 and the products added to it (at most
+// 2^15 x 2^15 a term) have room.  A column's own exponent (col_exp_w) goes past this only where its
+// largest value is below 2^-90 of the seed, i.e. where it adds nothing to the seed in fp32; without
+// the cap such a column (relu(h) of a nearly-off hidden layer) scaled a finite seed to inf.
+__device__ __forceinline__ int seed_exp_cap(float m, int wexp) {
+    return max(250 - ((__float_as_int(m) >> 23) & 0xff) - wexp, -126);
 }
 // acc += A B over one K = 16 step: A's two split images at img and img + img_stride
 __device__ __forceinline__ f32x16_t mfma3h(const _Float16 *img, const f16x8_t &b0, const f16x8_t &b1, f32x16_t acc,

@@ -1747,23 +1747,39 @@ extern "C" int ldpc_gnn_forward_train(const ldpc_gnn_plan *p, int hidden, int ty
                                       const float *d_weights, const int32_t *d_msg_type, const int32_t *d_msg_var,
                                       const float *d_llr, int N, int64_t B, float *d_probs, float *d_saved,
                                       void *d_work, int64_t work_bytes, void *stream) {
-    return ldpc_gnn_forward_train_ex(p, hidden, types, layers, d_weights, d_msg_type, d_msg_var, d_llr, N, B, d_probs,
-                                     d_saved, nullptr, d_work, work_bytes, stream);
+    return ldpc_gnn_forward_train_ex2(p, hidden, types, layers, d_weights, d_msg_type, d_msg_var, d_llr, N, B, d_probs,
+                                      d_saved, nullptr, 0, nullptr, d_work, work_bytes, stream);
 }
 
 extern "C" int ldpc_gnn_forward_train_ex(const ldpc_gnn_plan *p, int hidden, int types, int layers,
                                          const float *d_weights, const int32_t *d_msg_type, const int32_t *d_msg_var,
                                          const float *d_llr, int N, int64_t B, float *d_probs, float *d_saved,
                                          float *d_proj, void *d_work, int64_t work_bytes, void *stream) {
+    return ldpc_gnn_forward_train_ex2(p, hidden, types, layers, d_weights, d_msg_type, d_msg_var, d_llr, N, B, d_probs,
+                                      d_saved, d_proj, 0, nullptr, d_work, work_bytes, stream);
+}
+
+extern "C" int ldpc_gnn_forward_train_ex2(const ldpc_gnn_plan *p, int hidden, int types, int layers,
+                                          const float *d_weights, const int32_t *d_msg_type, const int32_t *d_msg_var,
+                                          const float *d_llr, int N, int64_t B, float *d_probs, float *d_saved,
+                                          float *d_proj, int flags, int *flags_used, void *d_work, int64_t work_bytes,
+                                          void *stream) {
     if (!p) return fail(LDPC_EINVAL, "plan is NULL");
+    if (flags & ~(LDPC_GNN_FP32_PRODUCTS | LDPC_GNN_CHECK_RANGE)) return fail(LDPC_EINVAL, "unknown flags");
+    if (flags_used) *flags_used = flags & LDPC_GNN_FP32_PRODUCTS;
     if (hidden <= 0 || hidden > kMaxTrainH || types <= 0 || layers <= 0 || N <= 0 || B < 0)
         return fail(LDPC_EINVAL, "bad dimensions (training needs hidden_dim <= 1024)");
     if (B == 0) return LDPC_OK;
     if (!d_weights || !d_msg_type || !d_msg_var || !d_llr || !d_probs || !d_saved)
         return fail(LDPC_EINVAL, "NULL tensor");
     if (d_proj && gnn_proj_floats(p, hidden, B, layers) == 0) d_proj = nullptr;  // a path without the area
-    return gnn_fp32_forward(p, hidden, types, layers, d_weights, d_msg_type, d_msg_var, d_llr, N, B, d_probs, d_saved,
-                            d_work, work_bytes, static_cast<hipStream_t>(stream), d_proj);
+    bool ran_fp32 = false;
+    const int rc = gnn_fp32_forward(p, hidden, types, layers, d_weights, d_msg_type, d_msg_var, d_llr, N, B, d_probs,
+                                    d_saved, d_work, work_bytes, static_cast<hipStream_t>(stream), d_proj,
+                                    (flags & LDPC_GNN_FP32_PRODUCTS) != 0, (flags & LDPC_GNN_CHECK_RANGE) != 0,
+                                    &ran_fp32);
+    if (flags_used && ran_fp32) *flags_used = LDPC_GNN_FP32_PRODUCTS;
+    return rc;
 }
 
 extern "C" int ldpc_gnn_backward_ds(const ldpc_gnn_plan *p, int hidden, int types, int layers,
@@ -1772,9 +1788,9 @@ extern "C" int ldpc_gnn_backward_ds(const ldpc_gnn_plan *p, int hidden, int type
                                     const float *d_grad_probs, const float *d_saved, const float *d_layer_probs,
                                     const float *d_grad_layer_probs, float *d_grad_weights, void *d_work,
                                     int64_t work_bytes, void *stream) {
-    return ldpc_gnn_backward_ds_ex(p, hidden, types, layers, d_weights, d_msg_type, d_msg_var, d_llr, N, B, d_probs,
-                                   d_grad_probs, d_saved, nullptr, d_layer_probs, d_grad_layer_probs, d_grad_weights,
-                                   d_work, work_bytes, stream);
+    return ldpc_gnn_backward_ds_ex2(p, hidden, types, layers, d_weights, d_msg_type, d_msg_var, d_llr, N, B, d_probs,
+                                    d_grad_probs, d_saved, nullptr, d_layer_probs, d_grad_layer_probs, d_grad_weights,
+                                    0, d_work, work_bytes, stream);
 }
 
 extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int types, int layers,
@@ -1783,7 +1799,23 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
                                        const float *d_grad_probs, const float *d_saved, const float *d_proj,
                                        const float *d_layer_probs, const float *d_grad_layer_probs,
                                        float *d_grad_weights, void *d_work, int64_t work_bytes, void *stream) {
+    return ldpc_gnn_backward_ds_ex2(p, hidden, types, layers, d_weights, d_msg_type, d_msg_var, d_llr, N, B, d_probs,
+                                    d_grad_probs, d_saved, d_proj, d_layer_probs, d_grad_layer_probs, d_grad_weights,
+                                    0, d_work, work_bytes, stream);
+}
+
+extern "C" int ldpc_gnn_backward_ds_ex2(const ldpc_gnn_plan *p, int hidden, int types, int layers,
+                                        const float *d_weights, const int32_t *d_msg_type, const int32_t *d_msg_var,
+                                        const float *d_llr, int N, int64_t B, const float *d_probs,
+                                        const float *d_grad_probs, const float *d_saved, const float *d_proj,
+                                        const float *d_layer_probs, const float *d_grad_layer_probs,
+                                        float *d_grad_weights, int flags, void *d_work, int64_t work_bytes,
+                                        void *stream) {
     if (!p) return fail(LDPC_EINVAL, "plan is NULL");
+    if (flags & ~LDPC_GNN_FP32_PRODUCTS) return fail(LDPC_EINVAL, "unknown flags");
+    // the projections this backward recomputes run as the forward's did (its MLP kernels are
+    // three-term bf16 splits or fp32 MFMAs: fp32's range either way)
+    const bool fp32_products = (flags & LDPC_GNN_FP32_PRODUCTS) != 0;
     const int H = hidden, T = types, L = layers;
     if (H <= 0 || H > kMaxTrainH || T <= 0 || L <= 0 || N <= 0 || B < 0)
         return fail(LDPC_EINVAL, "bad dimensions (training needs hidden_dim <= 1024)");
@@ -1856,7 +1888,8 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
         const float *xj = j > 0 ? d_saved + (int64_t)(j - 1) * n : nullptr;
         float *pv = (j & 1) ? w.Mv1 : w.Mv, *pc = (j & 1) ? w.Mc1 : w.Mc;
         float *gv = (j & 1) ? w.Gs1v : w.da, *gc = (j & 1) ? w.Gs1c : w.db;
-        if (int rc = gnn_project_groups(p, T, d_weights, j, xj, d_msg_type, d_msg_var, d_llr, N, B, pv, pc, gv, gc, s2))
+        if (int rc = gnn_project_groups(p, T, d_weights, j, xj, d_msg_type, d_msg_var, d_llr, N, B, pv, pc, gv, gc, s2,
+                                        fp32_products))
             return rc;
         LDPC_HIP(hipEventRecord(ev_ready[j & 1], s2));
         return LDPC_OK;
@@ -1915,7 +1948,7 @@ extern "C" int ldpc_gnn_backward_ds_ex(const ldpc_gnn_plan *p, int hidden, int t
             LDPC_HIP(hipStreamWaitEvent(s, ev_ready[l & 1], 0));
         } else if (pj) {  // forward recompute: projected rows (Mv / Mc) and the group means (Gsv / Gsc)
             if (int rc = gnn_project_groups(p, T, d_weights, l, x, d_msg_type, d_msg_var, d_llr, N, B, Mv, Mc,
-                                            w.da, w.db, s))  // = Gsv / Gsc here
+                                            w.da, w.db, s, fp32_products))  // = Gsv / Gsc here
                 return rc;
         } else {  // group means of c (forward recompute)
             GmT g{};

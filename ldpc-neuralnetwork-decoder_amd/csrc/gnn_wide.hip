@@ -583,6 +583,18 @@ __global__ __launch_bounds__(WFused<H>::NTH, 1) void gnn_wide_mlp_kernel(WMlp A)
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
     const int wexp1 = A.wexp[0], wexp2 = A.wexp[1];
     const float bo = A.msg_out ? A.bo[0] : 0.0f;
+    // max |b2v + b2c| + max |emb| (uniform): with a row's largest |c| it bounds y's seed b2 + x, as
+    // |x| <= |c| + |emb| (seed_exp_cap)
+    float ybm = 0.0f;
+    {
+        float bm = 0.0f, em = 0.0f;
+        for (int i = lane; i < H; i += 64) bm = fmaxf(bm, fabsf(A.b2v[i] + A.b2c[i]));
+        for (int i = lane; i < A.T * H; i += 64) em = fmaxf(em, fabsf(A.emb[i]));
+        bm += em;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bm = fmaxf(bm, __shfl_xor(bm, o, 64));
+        ybm = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bm)));
+    }
 
     // passes: this XCD's tiles, NW per pass (one per wave) per workgroup
     const int64_t ntiles = (A.R + 31) / 32;
@@ -658,6 +670,9 @@ __global__ __launch_bounds__(WFused<H>::NTH, 1) void gnn_wide_mlp_kernel(WMlp A)
         cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
         const int cexp = col_exp_w(cm, wexp1);
         const float csc = pow2f(cexp), asc = pow2f(cexp + wexp1), iasc = pow2f(-cexp - wexp1);
+        // y is seeded with b2 (+ x) and scaled with relu(h)'s running exponent: that is capped where
+        // it would carry the seed past fp32's range (the first live slice sets the largest scale)
+        const int ycap = seed_exp_cap((A.residual ? cm : 0.0f) + ybm, wexp2);
         f16x8_t c0[KS], c1[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
@@ -710,7 +725,7 @@ __global__ __launch_bounds__(WFused<H>::NTH, 1) void gnn_wide_mlp_kernel(WMlp A)
             }
             hm = fmaxf(hm, __shfl_xor(hm, 32, 64));
             // the running exponent moves down only; a zero slice leaves it (its split is exact anyway)
-            const int e = col_exp_w(hm, wexp2);
+            const int e = min(col_exp_w(hm, wexp2), ycap);
             const int en = hm > 0.0f ? min(erun, e) : erun;
             if (en != erun) {
                 const int d = en + wexp2 - ys;

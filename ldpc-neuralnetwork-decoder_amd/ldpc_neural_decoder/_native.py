@@ -18,6 +18,7 @@ LDPC_ES_OFF, LDPC_ES_BATCH, LDPC_ES_FRAME = 0, 1, 2
 LDPC_OUT_U8, LDPC_OUT_F32 = 0, 1
 LDPC_GNN_EARLY_STOP = 1
 LDPC_GNN_FP32_PRODUCTS = 2
+LDPC_GNN_CHECK_RANGE = 4
 LDPC_EINVAL, LDPC_EHIP, LDPC_EUNSUPPORTED, LDPC_ENOMEM = -1, -2, -3, -4
 
 _P = ctypes.c_void_p
@@ -38,6 +39,9 @@ SIGNATURES = {
     "ldpc_gnn_custom_var_workspace_size": (_I64, [_P, ctypes.c_int, ctypes.c_int, _I64, ctypes.c_int]),
     "ldpc_gnn_custom_var_forward": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
                                                    ctypes.c_int, _I64, _P, _P, _I64, _P]),
+    "ldpc_gnn_custom_var_forward_ex": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
+                                                      ctypes.c_int, _I64, ctypes.c_int, _P, _P, _I64, _P]),
+    "ldpc_gnn_split_range_exceeded": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _F32, _P, _P]),
     "ldpc_custom_minsum_decode": (ctypes.c_int, [_P, _P, _I64, ctypes.c_int, _P, _P, _I64, _P]),
     "ldpc_flood_decode": (ctypes.c_int, [_P, ctypes.c_int, _P, _I64, ctypes.c_int, _F32, ctypes.c_int,
                                          ctypes.c_int, _P, _P, _P, _P, _P, _I64, _P]),
@@ -87,6 +91,11 @@ SIGNATURES = {
                                                  ctypes.c_int, _I64, _P, _P, _P, _P, _I64, _P]),
     "ldpc_gnn_backward_ds_ex": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
                                                ctypes.c_int, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "ldpc_gnn_forward_train_ex2": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
+                                                  ctypes.c_int, _I64, _P, _P, _P, ctypes.c_int, _P, _P, _I64, _P]),
+    "ldpc_gnn_backward_ds_ex2": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
+                                                ctypes.c_int, _I64, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int, _P, _I64,
+                                                _P]),
 }
 
 _lib = None

@@ -285,7 +285,7 @@ class CustomVariableMessageGNNDecoder(MessageGNNDecoder):
     messages of out_m + llr_v).  forward(...) returns (probs, None), or (probs, max over bits of
     the per-bit BCE) with ground truth, as the reference does.  Any hidden_dim up to 1024 (the
     reference's constructor takes any, MGD:765: 64 runs the split-MFMA kernels, other widths the tiled
-    fp32 kernels); clique / identity check adjacencies.  Kernels: ldpc_gnn_custom_var_forward
+    fp32 kernels); clique / identity check adjacencies.  Kernels: ldpc_gnn_custom_var_forward_ex
     (csrc/gnn.hip).  Oracle: oracle/oracle.py custom_variable_forward.
 
     Training: this build has no backward for the hybrid GNN.  With grad enabled and trainable
@@ -346,12 +346,14 @@ class CustomVariableMessageGNNDecoder(MessageGNNDecoder):
             chunk = max(1, min(B, limit, max(1, (budget - ws1) // max(per, 1))))
             wsb = N.check(lib.ldpc_gnn_custom_var_workspace_size(plan.handle, Hd, Nv, chunk, L))
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            # weights beyond the f16 splits' range (_split_range_ok, per weight version): fp32 products
+            flags = 0 if self._split_ok else N.LDPC_GNN_FP32_PRODUCTS
             with torch.no_grad():
                 for s in range(0, B, chunk):
                     n = min(chunk, B - s)
-                    N.check(lib.ldpc_gnn_custom_var_forward(
+                    N.check(lib.ldpc_gnn_custom_var_forward_ex(
                         plan.handle, Hd, T, L, N.ptr(blob), N.ptr(types), N.ptr(io_map), N.ptr(llr[s:s + n]), Nv, n,
-                        N.ptr(probs[s:s + n]), N.ptr(ws), wsb, N.stream_ptr(dev)))
+                        flags, N.ptr(probs[s:s + n]), N.ptr(ws), wsb, N.stream_ptr(dev)))
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             probs = _NoHybridBackward.apply(probs, *[p for p in self.parameters() if p.requires_grad])
         if home != dev:

@@ -27,6 +27,7 @@ Compatibility notes (each mirrors the reference line cited):
     path (fp32 or bf16, chunked to LDPC_GNN_WORKSPACE_BYTES).  ``decode()`` is always inference.
     ``ground_truth`` returns (probs, BCE loss) as in :313-315.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -253,8 +254,9 @@ class MessageGNNDecoder(nn.Module):
         left halves, W2v, W2c and W1v_left + W1v_right.  H = 96..256 (csrc/gnn_wide.hip): each side's
         W1 right half (the projections: one scale per workgroup slice; checked per whole matrix, which
         is stricter), both sides' W1 left halves together and W2v | W2c (the fused MLP's two scales).
-        Checked once per weight version; otherwise the forward runs the products on the fp32 MFMA /
-        as bf16x6 splits (LDPC_GNN_FP32_PRODUCTS)."""
+        Checked once per weight version (inference, the hybrid decoder); otherwise the forward runs
+        the products on the fp32 MFMA / as bf16x6 splits (LDPC_GNN_FP32_PRODUCTS).  The training
+        forward makes the same decision on the device at every step (LDPC_GNN_CHECK_RANGE)."""
         H = self.hidden_dim
         wide = H != 64 and H % 32 == 0 and 96 <= H <= 256
         if H != 64 and not wide:
@@ -428,24 +430,31 @@ class _NativeGnnTrain(torch.autograd.Function):
         probs = torch.empty((B, Nv), dtype=torch.float32, device=dev)
         saved = torch.empty((L, B, E, H), dtype=torch.float32, device=dev)
         proj = torch.empty(npj, dtype=torch.float32, device=dev)
+        # H = 64 trains on the f16-split kernels (other widths on fp32 fma chains): weights beyond the
+        # splits' range take the fp32 products, as in inference.  These weights are new at every step, so
+        # the forward decides on the device (one synchronise, with only its layers left to launch) and
+        # reports what it ran with, for the backward.
+        used = ctypes.c_int(0)
         if B:
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            N.check(N.lib().ldpc_gnn_forward_train_ex(
+            N.check(N.lib().ldpc_gnn_forward_train_ex2(
                 plan.handle, H, T, L, N.ptr(blob), N.ptr(types), N.ptr(io_map), N.ptr(llr), Nv, B,
-                N.ptr(probs), N.ptr(saved), N.ptr(proj) if npj else None, N.ptr(ws), wsb, N.stream_ptr(dev)))
+                N.ptr(probs), N.ptr(saved), N.ptr(proj) if npj else None,
+                N.LDPC_GNN_CHECK_RANGE if H == 64 else 0, ctypes.byref(used), N.ptr(ws), wsb, N.stream_ptr(dev)))
+        flags = used.value
         layer_probs = torch.empty((max(L - 1, 0) if all_layers else 0, B, Nv), dtype=torch.float32, device=dev)
         if all_layers and B and L > 1:
             N.check(N.lib().ldpc_gnn_layer_probs(
                 plan.handle, H, T, L, N.ptr(blob), N.ptr(io_map), N.ptr(llr), Nv, B, N.ptr(saved),
                 N.ptr(layer_probs), N.ptr(ws), wsb, N.stream_ptr(dev)))
         ctx.save_for_backward(llr, io_map, types, blob, probs, saved, layer_probs, proj)
-        ctx.meta = (plan, H, T, L, [p.shape for p in params])
+        ctx.meta = (plan, H, T, L, [p.shape for p in params], flags)
         return probs, layer_probs
 
     @staticmethod
     def backward(ctx, grad_probs, grad_layer_probs):
         llr, io_map, types, blob, probs, saved, layer_probs, proj = ctx.saved_tensors
-        plan, H, T, L, shapes = ctx.meta
+        plan, H, T, L, shapes, flags = ctx.meta
         dev = llr.device
         B, Nv = llr.shape
         grad = torch.empty_like(blob)
@@ -456,11 +465,11 @@ class _NativeGnnTrain(torch.autograd.Function):
         gl = None
         if grad_layer_probs is not None and layer_probs.numel():
             gl = grad_layer_probs.to(dev, torch.float32).contiguous()
-        N.check(N.lib().ldpc_gnn_backward_ds_ex(
+        N.check(N.lib().ldpc_gnn_backward_ds_ex2(
             plan.handle, H, T, L, N.ptr(blob), N.ptr(types), N.ptr(io_map), N.ptr(llr), Nv, B,
             N.ptr(probs), N.ptr(g), N.ptr(saved), N.ptr(proj) if proj.numel() else None,
             N.ptr(layer_probs) if gl is not None else None,
-            N.ptr(gl) if gl is not None else None, N.ptr(grad), N.ptr(ws), wsb, N.stream_ptr(dev)))
+            N.ptr(gl) if gl is not None else None, N.ptr(grad), flags, N.ptr(ws), wsb, N.stream_ptr(dev)))
         grads, off = [], 0
         for s in shapes:
             n = int(torch.Size(s).numel())

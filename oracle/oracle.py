@@ -153,7 +153,7 @@ def message_types(graph, base, z):
 
 # --------------------------------------------------------------------------- GNN (torch fp32)
 def gnn_forward(sd, llr, msg_var_io, edge_var, edge_chk, num_vars, num_checks, types=None,
-                ground_truth=None, all_layers=False, dtype=None):
+                ground_truth=None, all_layers=False, dtype=None, features=None):
     """MessageGNNDecoder.forward restated (message_gnn_decoder.py:190-317).
 
     all_layers  (training extension, no reference counterpart) return the (L, B, N) probs of every
@@ -161,6 +161,8 @@ def gnn_forward(sd, llr, msg_var_io, edge_var, edge_chk, num_vars, num_checks, t
                 forward_all_layers / deep supervision); the last entry is the reference's probs.
     dtype       None: float32, the reference's arithmetic; torch.float64 gives the exact-arithmetic
                 yardstick the fp32 kernels' errors are measured against
+    features    a list that receives every layer's output features (B, E, H), for tests that need to
+                know what a layer was given
 
     sd          state_dict (tensors) in the reference's key schema
     msg_var_io  (E,) int64 message->variable index used for the LLR gather and the output sum
@@ -209,28 +211,35 @@ def gnn_forward(sd, llr, msg_var_io, edge_var, edge_chk, num_vars, num_checks, t
         y = mlp(p + "var_to_check_update", torch.cat([c, a], 2)) + \
             mlp(p + "check_to_var_update", torch.cat([c, b], 2))
         x = y + x if i > 0 else y
+        if features is not None:
+            features.append(x)
         if all_layers and i < n_layers - 1:
             per_layer.append(head(x))
     probs = head(x)
     if all_layers:
         return torch.stack(per_layer + [probs])
     if ground_truth is not None:
-        return probs, F.binary_cross_entropy(probs, torch.as_tensor(ground_truth).float())
+        return probs, F.binary_cross_entropy(probs, torch.as_tensor(ground_truth).to(dt))
     return probs
 
 
 def custom_variable_forward(sd, llr, msg_var_io, edge_chk, num_vars, num_checks, types=None, check_identity=False,
-                            ground_truth=None):
+                            ground_truth=None, dtype=None):
     """CustomVariableMessageGNNDecoder.forward (message_gnn_decoder.py:798-879, layer :672-755) under the
     semantics this build defines for it (models/custom_decoders.py; the reference cannot run it):
     per layer the check side's MLP over [c; A_c c] (A_c = group mean over the check's messages, or the
     identity), the layer's output head on it, the damped min-sum variable update on those LLRs and the
     decoder's Linear(1, H) back to features; output = sigmoid(mean of the last head over a variable's
-    messages + llr).  torch fp32; returns probs, or (probs, max per-bit BCE) with ground truth."""
+    messages + llr).  torch fp32 (dtype None), or the same math in `dtype` (torch.float64: the yardstick
+    the fp32 kernels' errors are measured against); returns probs, or (probs, max per-bit BCE) with
+    ground truth."""
     import torch
     import torch.nn.functional as F
 
-    llr = torch.as_tensor(llr, dtype=torch.float32)
+    dt = dtype or torch.float32
+    llr = torch.as_tensor(llr).to(dt)
+    if dtype is not None:
+        sd = {k: v.to(dt) for k, v in sd.items()}
     mv = torch.as_tensor(msg_var_io, dtype=torch.long)
     ec = torch.as_tensor(edge_chk, dtype=torch.long)
     B, E = llr.shape[0], mv.numel()
@@ -238,8 +247,8 @@ def custom_variable_forward(sd, llr, msg_var_io, edge_chk, num_vars, num_checks,
     w_in, b_in = sd["input_embedding.weight"][:, 0], sd["input_embedding.bias"]
     x = llr[:, mv].unsqueeze(-1) * w_in + b_in
     t = torch.zeros(E, dtype=torch.long) if types is None else torch.as_tensor(types).long()
-    deg_c = torch.bincount(ec, minlength=num_checks).float()
-    deg_v = torch.bincount(mv, minlength=num_vars).float()
+    deg_c = torch.bincount(ec, minlength=num_checks).to(dt)
+    deg_v = torch.bincount(mv, minlength=num_vars).to(dt)
 
     def mlp(p, z):
         h = torch.relu(z @ sd[p + ".0.weight"].T + sd[p + ".0.bias"])
@@ -252,42 +261,45 @@ def custom_variable_forward(sd, llr, msg_var_io, edge_chk, num_vars, num_checks,
         if check_identity:
             b = c
         else:
-            s = torch.zeros(B, num_checks, c.shape[-1]).index_add_(1, ec, c)
+            s = torch.zeros(B, num_checks, c.shape[-1], dtype=dt).index_add_(1, ec, c)
             b = (s / deg_c.clamp(min=1).view(1, -1, 1))[:, ec]
         Fm = mlp(p + "check_to_var_update", torch.cat([c, b], 2))
         lm = Fm @ sd[p + "output_projection.weight"][0] + sd[p + "output_projection.bias"][0]
-        tot = llr + torch.zeros(B, num_vars).index_add_(1, mv, lm)
+        tot = llr + torch.zeros(B, num_vars, dtype=dt).index_add_(1, mv, lm)
         v2c = tot[:, mv] - lm
         v2c = 0.5 * v2c + 0.5 * lm
         x = (v2c.unsqueeze(-1) * w_in + b_in) + Fm
     last = f"gnn_layers.{n_layers - 1}.output_projection."
     out = (x @ sd[last + "weight"][0]) + sd[last + "bias"][0]
     w = 1.0 / (deg_v + 1e-10)
-    var_llrs = torch.zeros(B, num_vars).index_add_(1, mv, out * w[mv])
+    var_llrs = torch.zeros(B, num_vars, dtype=dt).index_add_(1, mv, out * w[mv])
     probs = torch.sigmoid(var_llrs + llr)
     if ground_truth is not None:
-        loss = F.binary_cross_entropy(probs, torch.as_tensor(ground_truth).float(), reduction="none")
+        loss = F.binary_cross_entropy(probs, torch.as_tensor(ground_truth).to(dt), reduction="none")
         return probs, loss.max(dim=1).values
     return probs
 
 
-def gnn_forward_dense(sd, llr, msg_var_io, num_vars, Av, Ac, types=None):
+def gnn_forward_dense(sd, llr, msg_var_io, num_vars, Av, Ac, types=None, dtype=None):
     """MessageGNNDecoder.forward restated with the reference's own aggregation: dense
     bmm(A, x + emb) with whatever adjacencies are given, zero-padded / cropped to E as
     message_gnn_decoder.py:92-104 does (MessageGNNLayer.forward :51-129, decoder :190-317).  Used
     to pin the general-adjacency path; gnn_forward above is the segment-mean form of the same math
-    for the TannerToMessageGraph cliques."""
+    for the TannerToMessageGraph cliques.  dtype as in gnn_forward (None: float32)."""
     import torch
 
-    llr = torch.as_tensor(llr, dtype=torch.float32)
+    dt = dtype or torch.float32
+    llr = torch.as_tensor(llr).to(dt)
+    if dtype is not None:
+        sd = {k: v.to(dt) for k, v in sd.items()}
     mv = torch.as_tensor(msg_var_io, dtype=torch.long)
     B, E = llr.shape[0], mv.numel()
     n_layers = len({k.split(".")[1] for k in sd if k.startswith("gnn_layers.")})
     x = llr[:, mv].unsqueeze(-1) * sd["input_embedding.weight"][:, 0] + sd["input_embedding.bias"]
     t = torch.zeros(E, dtype=torch.long) if types is None else torch.as_tensor(types).long()
-    Av, Ac = torch.as_tensor(Av, dtype=torch.float32), torch.as_tensor(Ac, dtype=torch.float32)
+    Av, Ac = torch.as_tensor(Av).to(dt), torch.as_tensor(Ac).to(dt)
     if Av.size(0) != E or Av.size(1) != E:  # :92-104
-        nv, nc = torch.zeros(E, E), torch.zeros(E, E)
+        nv, nc = torch.zeros(E, E, dtype=dt), torch.zeros(E, E, dtype=dt)
         k = min(Av.size(0), E)
         nv[:k, :k] = Av[:k, :k]
         nc[:k, :k] = Ac[:k, :k]
@@ -307,7 +319,7 @@ def gnn_forward_dense(sd, llr, msg_var_io, num_vars, Av, Ac, types=None):
         x = y + x if i > 0 else y
     last = f"gnn_layers.{n_layers - 1}.output_projection."
     out = (x @ sd[last + "weight"][0]) + sd[last + "bias"][0]
-    var_llrs = torch.zeros(B, num_vars).index_add_(1, mv, out)
+    var_llrs = torch.zeros(B, num_vars, dtype=dt).index_add_(1, mv, out)
     return torch.sigmoid(var_llrs + llr)
 
 

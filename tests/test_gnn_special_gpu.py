@@ -30,6 +30,8 @@ import torch
 
 from conftest import ROOT, code_path
 
+import f64_ref as R
+
 from ldpc_neural_decoder.models import create_message_gnn_decoder
 from ldpc_neural_decoder.utils import awgn_llr, expand_base_matrix, load_base_matrix
 
@@ -243,3 +245,40 @@ def test_wide_fused_hidden_slice_scales(cuda, oracle_mod, hidden):
     print(f"H={hidden}: native {err:.3e}  oracle-f32 {ref_err:.3e}  (unsaturated {unsure:.3f})")
     assert unsure > 0.01
     assert err <= 2 * ref_err + 1e-7, (err, ref_err)
+
+
+_NEARLY_OFF = [(c, "inference") for c in R.NEARLY_OFF_CASES] + [(c, "train") for c in R.NEARLY_OFF_CASES if c[1] == 64]
+
+
+@pytest.mark.parametrize("case,path", _NEARLY_OFF,
+                         ids=[f"z{c[0]}-H{c[1]}-L{c[2]}-off{c[3]}-{c[4]}-x{c[5]:g}-{p}" for c, p in _NEARLY_OFF])
+def test_split_mlp_nearly_off_hidden_layer(cuda, oracle_mod, case, path):
+    """One layer whose hidden units are nearly off: W1 = 0 and b1 = 1e-30 in both MLPs (or, "first32",
+    in the first 32 hidden units of the var side alone: the fused wide kernel's first live slice is
+    tiny).  relu(h)'s largest value is then 1e-30, which gnn_mlp2s_kernel and gnn_wide_mlp_kernel
+    scale to about 2^14 -- and y's accumulators, seeded with b2 + x, by the same power of two times
+    the weights' scale, 2^126 at most.  With LLRs (randn * 2 + 1) * 8 the seed stays below 4 and so
+    finite; * 32 takes it past 4 on a good tenth of the messages of a layer with a residual, where an uncapped scale
+    overflows a finite frame to inf and its probs to NaN while the reference returns finite probs.  Zero rows do not count against the splits' range, so the split / fused kernels run.
+    Bar: every prob finite and within 2x the fp32 oracle's own error against float64, + 1e-7 (inputs
+    checked finite and unsaturated in tests/test_f64_ref_host.py).  "train": the training forward."""
+    z, hidden, layers, off, units, scale = case
+    H, dec, conv, types, llr = R.nearly_off_case(*case)
+    p64, p32 = R.forward_pair(oracle_mod, dec, conv, H, types, llr)
+    dec = dec.to(cuda)
+    if path == "train":
+        got = dec(llr.to(cuda), conv.message_to_var_index(), types, conv.var_to_check_adjacency,
+                  conv.check_to_var_adjacency)
+        assert got.requires_grad
+        got = got.detach()
+    else:
+        got = _native(dec, conv, types, llr.to(cuda), cuda)
+        assert dec._split_ok
+    got = got.cpu().double()
+    err32 = float((p32.double() - p64).abs().max())
+    bad = int((~torch.isfinite(got)).sum())
+    err = float((got - p64).abs().nan_to_num(nan=float("inf")).max())
+    print(f"nearly-off z{z} H{hidden} layer {off} {units} x{scale:g} {path}: native {err:.3e} ({bad} non-finite)  "
+          f"oracle-f32 {err32:.3e}  bar {2 * err32 + 1e-7:.3e}  (unsaturated {R.unsaturated(p64):.3f})")
+    assert bad == 0, f"{bad} of {got.numel()} probs are not finite"
+    assert err <= 2 * err32 + 1e-7, (err, err32)
