@@ -35,7 +35,7 @@ enum {
     LDPC_ENOMEM = -4
 };
 
-enum { LDPC_ALGO_MINSUM = 0, LDPC_ALGO_BP = 1, LDPC_ALGO_LAYERED_MINSUM = 2 };
+enum { LDPC_ALGO_MINSUM = 0, LDPC_ALGO_BP = 1, LDPC_ALGO_LAYERED_MINSUM = 2, LDPC_ALGO_LAYERED_MINSUM_ANY = 3 };
 enum { LDPC_ES_OFF = 0, LDPC_ES_BATCH = 1, LDPC_ES_FRAME = 2 };
 enum { LDPC_OUT_U8 = 0, LDPC_OUT_F32 = 1 };
 
@@ -116,12 +116,42 @@ int ldpc_graph_edges(const ldpc_graph *g, int32_t *h_edge_chk, int32_t *h_edge_v
  *   a divisor of 64, LDS need above a CU's, or LDPC_FLOOD_STREAM set) is LDPC_EUNSUPPORTED.
  * d_work: ldpc_flood_workspace_size of the same arguments suffices, when required as above.
  * Non-finite LLRs: the call returns and every output is 0 or 1; the outputs of a frame holding a
+ *   NaN or an infinity are otherwise unspecified, the other frames of the batch are unaffected.
+ *
+ * Layered min-sum on any graph (algo LDPC_ALGO_LAYERED_MINSUM_ANY).  The same algorithm, word for word:
+ * the "Layered min-sum" text above is its definition, and d_bits, d_iters, d_batch_iters and d_counters
+ * mean the same.  LDPC_ES_BATCH is LDPC_EINVAL here too.  What differs is where it runs:
+ *   - on a graph that the flooding algos decode LDS-resident (and LDPC_FLOOD_STREAM unset) it is
+ *     LDPC_ALGO_LAYERED_MINSUM itself: the same kernels, the same d_work rule, and the same
+ *     LDPC_EUNSUPPORTED if the layered schedule (posteriors and messages of a wave's frames) does not fit
+ *     a CU's LDS while the flooding one does;
+ *   - on a graph that the flooding algos decode on the streaming kernels (lifting not a divisor of 64,
+ *     LDS need above a CU's, or LDPC_FLOOD_STREAM set) it runs streaming kernels of its own: posteriors
+ *     and messages in d_work, the checks cut into runs (ldpc_layered_runs below) and one launch per run
+ *     and check degree, per iteration.  Same results as the LDS-resident kernels, bit for bit.  A
+ *     check or variable degree above 32 is LDPC_EUNSUPPORTED, as for the streaming flooding decoders.
+ * d_work: ldpc_flood_workspace_size of the same arguments suffices; on the streaming path it is
+ *   required (LDPC_EINVAL without it), as for the streaming flooding decoders.
+ * Non-finite LLRs: the call returns and every output is 0 or 1; the outputs of a frame holding a
  *   NaN or an infinity are otherwise unspecified, the other frames of the batch are unaffected. */
 int64_t ldpc_flood_workspace_size(const ldpc_graph *g, int64_t B, int max_iter, int early_stop);
 int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_llr, int64_t B, int max_iter,
                       float alpha, int early_stop, int out_dtype, void *d_bits, int32_t *d_iters,
                       int32_t *d_batch_iters, uint64_t *d_counters, void *d_work,
                       int64_t work_bytes, void *stream);
+/* The layers of the streaming layered decoder, as host words (for unit tests; no device is touched).  The
+ * arguments of ldpc_graph_create, then a buffer of `capacity` 32-bit words.  Returns the words needed (or a
+ * negative error, as ldpc_graph_create would) and fills h_words when capacity holds them (h_words may be
+ * NULL to ask for the size).  A run is a maximal stretch of consecutive checks, in ascending index, whose
+ * variable sets are pairwise disjoint, built greedily: check i joins the current run unless one of its
+ * variables is already in it, and then opens the next.  Layout:
+ *   n_runs, n_seg
+ *   run_ptr[n_runs + 1]  check indices: run r is the checks run_ptr[r] .. run_ptr[r + 1] - 1
+ *   seg[n_seg][4]        {run, degree, offset into order, count}: runs ascending, degrees ascending inside
+ *                        a run (a check without edges: a degree-0 segment, which launches nothing)
+ *   order[M]             check indices, ascending inside a segment */
+int64_t ldpc_layered_runs(int M, int N, int64_t E, const int32_t *h_edge_chk, const int32_t *h_edge_var,
+                          int32_t *h_words, int64_t capacity);
 /* How many frame groups (64 / Z frames each: group i holds frames i * 64 / Z ..) the last
  * ldpc_flood_decode with these arguments and this d_work decoded a second time (see d_work above),
  * and, when h_groups is given (room for ceil(B / (64 / Z)) entries), which, in no particular order.

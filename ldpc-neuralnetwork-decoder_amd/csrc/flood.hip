@@ -25,7 +25,8 @@
 // Compile with -ffp-contract=off: no a*b+c may fuse on this path.
 // Translation units: flood_dev.hpp (device code shared by all), flood_fixed_ms.hip / flood_fixed_bp.hip
 // (compile-time schedules: flood_fixed.hpp), flood_stream.hip (streaming decoders), flood_layered.hip
-// (layered min-sum), and this file (table-driven kernel, early-stop passes, host dispatch, the C ABI).
+// (layered min-sum), flood_layered_stream.hip (layered min-sum on the streaming layout), and this file
+// (table-driven kernel, early-stop passes, host dispatch, the C ABI).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -363,20 +364,26 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
                                  void *d_bits, int32_t *d_iters, int32_t *d_batch_iters,
                                  uint64_t *d_counters, void *d_work, int64_t work_bytes, void *stream) {
     if (!g) return fail(LDPC_EINVAL, "graph is NULL");
-    if (algo != LDPC_ALGO_MINSUM && algo != LDPC_ALGO_BP && algo != LDPC_ALGO_LAYERED_MINSUM)
+    if (algo != LDPC_ALGO_MINSUM && algo != LDPC_ALGO_BP && algo != LDPC_ALGO_LAYERED_MINSUM &&
+        algo != LDPC_ALGO_LAYERED_MINSUM_ANY)
         return fail(LDPC_EINVAL, "unknown algo");
+    const bool layered = algo == LDPC_ALGO_LAYERED_MINSUM || algo == LDPC_ALGO_LAYERED_MINSUM_ANY;
     if (early_stop < 0 || early_stop > 2) return fail(LDPC_EINVAL, "unknown early_stop mode");
     if (out_dtype != LDPC_OUT_U8 && out_dtype != LDPC_OUT_F32) return fail(LDPC_EINVAL, "unknown out_dtype");
     if (B < 0) return fail(LDPC_EINVAL, "negative batch");
     if (max_iter < 1 || max_iter > 1024) return fail(LDPC_EINVAL, "max_iter must be in [1, 1024]");
-    if (algo == LDPC_ALGO_LAYERED_MINSUM && early_stop == LDPC_ES_BATCH)
+    if (layered && early_stop == LDPC_ES_BATCH)
         return fail(LDPC_EINVAL, "layered min-sum has no batch-global stop (LDPC_ES_BATCH mirrors the reference's "
                                  "flooding classes): use LDPC_ES_OFF or LDPC_ES_FRAME");
     if (B == 0) return LDPC_OK;
     if (!d_llr || !d_bits) return fail(LDPC_EINVAL, "llr / bits is NULL");
     const bool streaming = use_stream(g, early_stop);
-    if (algo == LDPC_ALGO_LAYERED_MINSUM) {
-        // LDS-resident only: a streaming layered decoder would be one launch per layer
+    // LDPC_ALGO_LAYERED_MINSUM_ANY on a streaming graph: the streaming layered decoder, one launch per layer
+    // segment (flood_layered_stream.hip); elsewhere it is LDPC_ALGO_LAYERED_MINSUM, refusals included (the
+    // workspace query sizes the LDS-resident decoders' scratch there, not the streaming arrays)
+    const bool layered_stream = algo == LDPC_ALGO_LAYERED_MINSUM_ANY && streaming;
+    if (layered && !layered_stream) {
+        // LDS-resident only
         if (streaming)
             return fail(LDPC_EUNSUPPORTED,
                         "layered min-sum needs the LDS-resident schedule, and this graph decodes on the streaming "
@@ -403,7 +410,8 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
     }
     const FloodCall c{g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits, d_iters, d_counters, d_batch_iters,
                       d_work, s};
-    if (algo == LDPC_ALGO_LAYERED_MINSUM) return run_layered(c);
+    if (layered_stream) return run_layered_stream(c);
+    if (layered) return run_layered(c);
     if (streaming) return run_stream_decode(algo, c);
     return algo == LDPC_ALGO_MINSUM ? run_flood<LDPC_ALGO_MINSUM>(c) : run_flood<LDPC_ALGO_BP>(c);
 }

@@ -47,6 +47,10 @@ int launch_fixed(const FloodCall &c, int es, size_t lds, const Outs &O, const Es
 size_t layered_lds_bytes(const ldpc_graph *g, int es);
 int run_layered(const FloodCall &c);
 
+// flood_layered_stream.hip: layered min-sum on the streaming layout (any graph with check degrees up to
+// kStreamMaxDeg; c.es is LDPC_ES_OFF or LDPC_ES_FRAME).  c.work is the streaming workspace (stream_ws_bytes).
+int run_layered_stream(const FloodCall &c);
+
 // flood_stream.hip: the streaming decoders (messages in HBM, any graph)
 int64_t stream_ws_bytes(const ldpc_graph *g, int64_t B, int max_iter);
 int run_stream_decode(int algo, const FloodCall &c);

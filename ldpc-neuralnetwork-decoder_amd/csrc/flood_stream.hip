@@ -4,7 +4,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "flood_host.hpp"
+#include "flood_stream.hpp"
 
 namespace ldpc {
 
@@ -17,32 +17,7 @@ namespace ldpc {
 // operation sequences are the LDS kernels' (= the reference's), so results are bit-identical
 // (min-sum) / identical (BP) across the two paths.  Early stop keeps the reference's rules with
 // device flags: a finished batch (LDPC_ES_BATCH) or frame (LDPC_ES_FRAME) skips the later launches.
-struct StreamArgs {
-    const int32_t *chk_ptr, *ev, *var_ptr, *var_edge;
-    int M, N;
-    int64_t E, B;
-    float *msg;        // [E][B] v2c / c2v in place
-    float *llrT;       // [N][B]
-    uint8_t *bitsT;    // [N][B] hard decisions of the latest iteration
-    uint8_t *done;     // [B] LDPC_ES_FRAME: frame frozen
-    int32_t *iters;    // [B] LDPC_ES_FRAME: iterations of a frozen frame
-    int32_t *ctl;      // [0] batch stopped  [1] batch iterations
-    int32_t *invalid;  // [max_iter] LDPC_ES_BATCH: frames failing H x = 0 after each iteration
-    float alpha;
-    int es;
-    // flooding decoders only (null for the hybrid min-sum): per edge, its variable when that has
-    // degree 1.  Such an edge's v2c is the channel LLR forever, so the check phase leaves it in
-    // place and takes the variable's decision itself (APP = llr + c2v = v2c + c2v, the same
-    // float add); the degree-1 variables get no variable-phase launch.
-    const int32_t *ext_var;
-};
-
-__device__ __forceinline__ bool stream_skip(const StreamArgs &S, int64_t b) {
-    if (S.es == LDPC_ES_BATCH) return S.ctl[0] != 0;
-    if (S.es == LDPC_ES_FRAME) return S.done[b] != 0;
-    return false;
-}
-
+// StreamArgs, the workspace carve and the passes that flood_layered_stream.hip runs too: flood_stream.hpp.
 // (B, N) -> (N, B) through 64 x 64 LDS tiles
 __global__ __launch_bounds__(256) void stream_transpose_llr_kernel(const float *__restrict__ llr, int64_t B, int N,
                                                                    float *__restrict__ llrT) {
@@ -124,10 +99,6 @@ __device__ __forceinline__ void stream_row(const StreamArgs &S, float *m, int e0
         }
     }
 }
-
-#define LDPC_STREAM_DEG_CASES(X)                                                                       \
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) \
-    X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
 
 // one launch per check degree DC (graph.cpp groups the checks by degree): thread = (k-th check of
 // the degree, frame), the frame fastest, so a wave is 64 frames of one check (coalesced rows)
@@ -340,15 +311,6 @@ __global__ __launch_bounds__(256) void custom_output_kernel(StreamArgs S, float 
 }
 
 
-namespace {
-struct StreamWs {
-    float *msg, *llrT;
-    uint8_t *bitsT, *done;
-    int32_t *iters, *ctl, *invalid;
-    uint32_t *partials;
-    int64_t bytes;
-};
-
 StreamWs stream_ws(const ldpc_graph *g, int64_t B, int max_iter, void *base) {
     StreamWs w{};
     char *p = static_cast<char *>(base);
@@ -366,10 +328,10 @@ StreamWs stream_ws(const ldpc_graph *g, int64_t B, int max_iter, void *base) {
     return w;
 }
 
+namespace {
 // one launch per node degree (graph.cpp groups the checks / variables by degree), on a 2-D grid
 // (frames, nodes) so a thread finds its (node, frame) without a 64-bit division; grid.y is
-// chunked to 65535 nodes
-constexpr int kGridY = 65535;
+// chunked to kGridY nodes
 template <class F>
 void per_degree(const std::vector<int> &seg, const int32_t *order, int64_t B, F &&launch) {
     const unsigned gx = (unsigned)((B + 255) / 256);
@@ -490,6 +452,21 @@ int run_custom_minsum_(const ldpc_graph *g, const float *llr, int64_t B, int ite
 }
 
 }  // namespace
+
+void launch_stream_transpose(const float *llr, int64_t B, int N, float *llrT, hipStream_t s) {
+    const dim3 tgrid((unsigned)((B + 63) / 64), (unsigned)((N + 63) / 64));
+    hipLaunchKernelGGL(stream_transpose_llr_kernel, tgrid, dim3(256), 0, s, llr, B, N, llrT);
+}
+
+void launch_stream_syndrome(const StreamArgs &S, int it, hipStream_t s) {
+    hipLaunchKernelGGL(stream_syndrome_kernel, dim3((unsigned)((S.B + 255) / 256)), dim3(256), 0, s, S, it);
+}
+
+void launch_stream_emit(const StreamArgs &S, int max_iter, int out_dtype, void *bits, int32_t *iters_out,
+                        uint32_t *partials, hipStream_t s) {
+    hipLaunchKernelGGL(stream_emit_kernel, dim3((unsigned)((S.B + 63) / 64)), dim3(256), 0, s, S, max_iter, out_dtype,
+                       bits, iters_out, partials);
+}
 
 int64_t stream_ws_bytes(const ldpc_graph *g, int64_t B, int max_iter) { return stream_ws(g, B, max_iter, nullptr).bytes; }
 

@@ -14,6 +14,7 @@
 #include "common.hpp"
 #include "gen/fixed_codes.hpp"
 #include "graph.hpp"
+#include "layered_runs.hpp"
 
 namespace ldpc {
 
@@ -79,9 +80,9 @@ void schedule(const std::vector<int> &tasks, const std::vector<double> &cost, in
 int build_csr(ldpc_graph *g) {
     const int M = g->M, N = g->N;
     const int64_t E = g->E;
-    std::vector<int32_t> blob((size_t)(M + 1) + E + (N + 1) + E + M + N + E, 0);
+    std::vector<int32_t> blob((size_t)(M + 1) + E + (N + 1) + E + M + N + E + M, 0);
     int32_t *cp = blob.data(), *ev = cp + M + 1, *vp = ev + E, *ve = vp + N + 1, *ro = ve + E, *co = ro + M,
-            *xv = co + N;
+            *xv = co + N, *lo = xv + E;
     for (int64_t e = 0; e < E; ++e) {
         ++cp[g->edge_chk[e] + 1];
         ev[e] = g->edge_var[e];
@@ -110,6 +111,11 @@ int build_csr(ldpc_graph *g) {
     }
     group(cp, M, ro, g->row_seg);
     group(vp, N, co, g->col_seg);
+    // the streaming layered decoder's runs (layered_runs.hpp): one launch per segment
+    LayeredRuns lr;
+    if (const char *msg = layered_runs(M, N, E, g->edge_chk.data(), g->edge_var.data(), lr)) return fail(LDPC_EINVAL, msg);
+    std::copy(lr.order.begin(), lr.order.end(), lo);
+    g->lay_seg = lr.seg;
     LDPC_HIP(hipMalloc(&g->d_csr, blob.size() * sizeof(int32_t)));
     LDPC_HIP(hipMemcpy(g->d_csr, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     g->chk_ptr = g->d_csr;
@@ -119,6 +125,7 @@ int build_csr(ldpc_graph *g) {
     g->row_order = g->var_edge + E;
     g->col_order = g->row_order + M;
     g->ext_var = g->col_order + N;
+    g->lay_order = g->ext_var + E;
     return LDPC_OK;
 }
 
@@ -334,6 +341,13 @@ extern "C" int ldpc_graph_create_qc(const int32_t *h_base, int mb, int nb, int z
     // inside a check row the vars must ascend: blocks are visited c ascending, and each block
     // contributes one var in [c*z, (c+1)*z), so the order is already ascending.
     return ldpc_graph_create(mb * z, nb * z, (int64_t)ec.size(), ec.data(), ev.data(), out);
+}
+
+extern "C" int64_t ldpc_layered_runs(int M, int N, int64_t E, const int32_t *h_edge_chk, const int32_t *h_edge_var,
+                                     int32_t *h_words, int64_t capacity) {
+    LayeredRuns t;
+    if (const char *msg = layered_runs(M, N, E, h_edge_chk, h_edge_var, t)) return fail(LDPC_EINVAL, msg);
+    return layered_runs_words(t, h_words, capacity);
 }
 
 extern "C" int ldpc_graph_destroy(ldpc_graph *g) {

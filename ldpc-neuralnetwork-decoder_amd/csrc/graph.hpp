@@ -82,4 +82,9 @@ struct ldpc_graph {
     const int32_t *row_order = nullptr, *col_order = nullptr;
     const int32_t *ext_var = nullptr;   // per edge: its variable if that has degree 1, else -1
     std::vector<int> row_seg, col_seg;  // {degree, offset into *_order, count} triples
+    // streaming layered decoder (flood_layered_stream.hip): the runs of layered_runs.hpp.  lay_order is its
+    // order[M] on the device, behind ext_var; lay_seg its {run, degree, offset into lay_order, count}
+    // quadruples, one launch each, kept on the host for the launch loop.
+    const int32_t *lay_order = nullptr;
+    std::vector<int32_t> lay_seg;
 };

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDPC_AMD_LIB", os.path.join(_HERE, "_lib", "libldpc_amd.so"))
 
-LDPC_ALGO_MINSUM, LDPC_ALGO_BP, LDPC_ALGO_LAYERED_MINSUM = 0, 1, 2
+LDPC_ALGO_MINSUM, LDPC_ALGO_BP, LDPC_ALGO_LAYERED_MINSUM, LDPC_ALGO_LAYERED_MINSUM_ANY = 0, 1, 2, 3
 LDPC_ES_OFF, LDPC_ES_BATCH, LDPC_ES_FRAME = 0, 1, 2
 LDPC_OUT_U8, LDPC_OUT_F32 = 0, 1
 LDPC_GNN_EARLY_STOP = 1
@@ -45,6 +45,7 @@ SIGNATURES = {
     "ldpc_custom_minsum_decode": (ctypes.c_int, [_P, _P, _I64, ctypes.c_int, _P, _P, _I64, _P]),
     "ldpc_flood_decode": (ctypes.c_int, [_P, ctypes.c_int, _P, _I64, ctypes.c_int, _F32, ctypes.c_int,
                                          ctypes.c_int, _P, _P, _P, _P, _P, _I64, _P]),
+    "ldpc_layered_runs": (_I64, [ctypes.c_int, ctypes.c_int, _I64, _P, _P, _P, _I64]),
     "ldpc_flood_redo_count": (ctypes.c_int, [_P, ctypes.c_int, _I64, ctypes.c_int, ctypes.c_int, _P, _P, _P,
                                                  _P]),
     "ldpc_bp_math_raw": (ctypes.c_int, [_P, _I64, _P, _P, _P]),

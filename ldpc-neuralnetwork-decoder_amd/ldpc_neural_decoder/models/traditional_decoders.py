@@ -138,11 +138,20 @@ class LayeredMinSumDecoder(_FloodDecoder):
     ``early_stopping=True`` and ``early_stopping="frame"`` BOTH mean the per-frame freeze (a frame
     stops at the first iteration whose decisions satisfy H x = 0); there is no batch-global rule,
     and ``iterations`` is then the largest per-frame count.  A graph without an LDS-resident
-    schedule (e.g. a lifting size that does not divide 64) raises ``NativeError``."""
+    schedule (e.g. a lifting size that does not divide 64) raises ``NativeError``.
+
+    ``any_graph=True`` lifts that last limit: such a graph then decodes on the streaming layered
+    kernels (csrc/flood_layered_stream.hip: posteriors and messages in device memory, one launch per
+    run of variable-disjoint checks and check degree), with the same decisions and iteration counts,
+    bit for bit; a graph that has an LDS-resident schedule runs exactly what the default runs.  Node
+    degrees above 32 raise ``NativeError`` on the streaming kernels, as for the flooding classes."""
     _algo = N.LDPC_ALGO_LAYERED_MINSUM
 
-    def __init__(self, H, max_iterations=50, scaling_factor=0.75, early_stopping=True):
+    def __init__(self, H, max_iterations=50, scaling_factor=0.75, early_stopping=True, any_graph=False):
         self.scaling_factor = scaling_factor
+        self.any_graph = bool(any_graph)
+        if self.any_graph:
+            self._algo = N.LDPC_ALGO_LAYERED_MINSUM_ANY
         super().__init__(H, max_iterations, early_stopping)
 
     def _alpha(self):
