@@ -35,7 +35,13 @@ enum {
     LDPC_ENOMEM = -4
 };
 
-enum { LDPC_ALGO_MINSUM = 0, LDPC_ALGO_BP = 1, LDPC_ALGO_LAYERED_MINSUM = 2, LDPC_ALGO_LAYERED_MINSUM_ANY = 3 };
+enum {
+    LDPC_ALGO_MINSUM = 0,
+    LDPC_ALGO_BP = 1,
+    LDPC_ALGO_LAYERED_MINSUM = 2,
+    LDPC_ALGO_LAYERED_MINSUM_ANY = 3,
+    LDPC_ALGO_MINSUM_F16 = 5 /* 4 is not assigned: it stays an unknown value (LDPC_EINVAL) */
+};
 enum { LDPC_ES_OFF = 0, LDPC_ES_BATCH = 1, LDPC_ES_FRAME = 2 };
 enum { LDPC_OUT_U8 = 0, LDPC_OUT_F32 = 1 };
 
@@ -133,7 +139,44 @@ int ldpc_graph_edges(const ldpc_graph *g, int32_t *h_edge_chk, int32_t *h_edge_v
  * d_work: ldpc_flood_workspace_size of the same arguments suffices; on the streaming path it is
  *   required (LDPC_EINVAL without it), as for the streaming flooding decoders.
  * Non-finite LLRs: the call returns and every output is 0 or 1; the outputs of a frame holding a
- *   NaN or an infinity are otherwise unspecified, the other frames of the batch are unaffected. */
+ *   NaN or an infinity are otherwise unspecified, the other frames of the batch are unaffected.
+ *
+ * Half-precision min-sum (algo LDPC_ALGO_MINSUM_F16 = 5; no reference counterpart, this text is its
+ * definition).  Flooding scaled min-sum on the Tanner graph.  Every value is IEEE binary16.  Every
+ * operation is rounded to nearest-even with gradual underflow.  No multiply-add is fused.  C = 1024 is
+ * the clamp.
+ *   Channel.   x[v] = clamp(half(llr[v]), -C, +C).  half() is the float32 -> binary16 conversion,
+ *              round-to-nearest-even.  A magnitude that rounds to infinity becomes +-C.  An infinite
+ *              LLR is therefore a defined input.
+ *   Scaling.   a = half(alpha).  Require 0 <= a <= 1, else LDPC_EINVAL.
+ *   Init.      v2c[e] = x[var(e)].
+ *   Check i with variables j_0 < ... < j_{d-1}:
+ *              c2v[i,k] = (prod_{q != k} sgn v2c[i,q]) * (a * min_{q != k} |v2c[i,q]|).
+ *              sgn(0) = 0.  The product of signs is formed first.  a * min is rounded once to binary16.
+ *   Variable j with checks i_0 < ... < i_{dv-1}:
+ *              v2c[i_k, j] = clamp(x[j] + sum_{q != k} c2v[i_q, j], -C, +C).  The sum is taken left to
+ *              right in ascending q, starting from x[j].  Each add is rounded.  A degree-1 variable's
+ *              v2c is x[j] forever.
+ *   Posterior. app[j] = x[j] + sum_q c2v[i_q, j], in the same order, unclamped.  bit[j] = (app[j] < 0).
+ * With a <= 1 and variable degree <= 32, no partial sum exceeds 33 * 1024 = 33 792 < 65 504.  Nothing
+ * ever overflows, so there is no bail-out and no redo path (ldpc_flood_redo_count: LDPC_EUNSUPPORTED).
+ *   - A variable degree above 32 is LDPC_EUNSUPPORTED.
+ *   - The sign of a zero is not part of the contract.  A row containing a zero has minimum 0, so
+ *     c2v = +-0, and `<` cannot tell the two zeros apart.  Decisions and iteration counts are defined,
+ *     message bits are not.
+ *   - NaN LLR.  That frame's outputs are 0 or 1 and otherwise unspecified.  Every other frame is
+ *     unaffected, the frame sharing its lanes included (the kernel packs two frames per lane).
+ *   - Early stop.  LDPC_ES_OFF and LDPC_ES_FRAME behave as for LDPC_ALGO_MINSUM: a frame freezes at the
+ *     first iteration whose decisions satisfy H x = 0, with that iteration's bits and count.
+ *     LDPC_ES_BATCH is LDPC_EINVAL, as for the layered algorithm.
+ *   - Graphs.  LDS-resident only.  A graph the flooding algorithms send to the streaming kernels is
+ *     LDPC_EUNSUPPORTED.  That covers a lifting that does not divide 64, an LDS need above a CU's
+ *     (here nslots * 256 + 8 + 2 * (Nb + 1) * 8 bytes), and LDPC_FLOOD_STREAM set.
+ *   - Outputs.  d_llr stays float32 (B, N).  d_bits, d_iters, d_batch_iters and d_counters mean what
+ *     they mean for LDPC_ALGO_MINSUM.
+ *   - Workspace.  ldpc_flood_workspace_size of the same arguments suffices.  It is required under the
+ *     same conditions as for LDPC_ALGO_MINSUM.
+ *   - ldpc_graph_set_variant has no effect on it: there is no compile-time schedule. */
 int64_t ldpc_flood_workspace_size(const ldpc_graph *g, int64_t B, int max_iter, int early_stop);
 int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_llr, int64_t B, int max_iter,
                       float alpha, int early_stop, int out_dtype, void *d_bits, int32_t *d_iters,

@@ -25,7 +25,8 @@
 // Compile with -ffp-contract=off: no a*b+c may fuse on this path.
 // Translation units: flood_dev.hpp (device code shared by all), flood_fixed_ms.hip / flood_fixed_bp.hip
 // (compile-time schedules: flood_fixed.hpp), flood_stream.hip (streaming decoders), flood_layered.hip
-// (layered min-sum), flood_layered_stream.hip (layered min-sum on the streaming layout), and this file
+// (layered min-sum), flood_layered_stream.hip (layered min-sum on the streaming layout), flood_half.hip
+// (half-precision min-sum, two frames per lane), and this file
 // (table-driven kernel, early-stop passes, host dispatch, the C ABI).
 #include <algorithm>
 #include <cstdio>
@@ -365,9 +366,10 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
                                  uint64_t *d_counters, void *d_work, int64_t work_bytes, void *stream) {
     if (!g) return fail(LDPC_EINVAL, "graph is NULL");
     if (algo != LDPC_ALGO_MINSUM && algo != LDPC_ALGO_BP && algo != LDPC_ALGO_LAYERED_MINSUM &&
-        algo != LDPC_ALGO_LAYERED_MINSUM_ANY)
+        algo != LDPC_ALGO_LAYERED_MINSUM_ANY && algo != LDPC_ALGO_MINSUM_F16)
         return fail(LDPC_EINVAL, "unknown algo");
     const bool layered = algo == LDPC_ALGO_LAYERED_MINSUM || algo == LDPC_ALGO_LAYERED_MINSUM_ANY;
+    const bool half = algo == LDPC_ALGO_MINSUM_F16;
     if (early_stop < 0 || early_stop > 2) return fail(LDPC_EINVAL, "unknown early_stop mode");
     if (out_dtype != LDPC_OUT_U8 && out_dtype != LDPC_OUT_F32) return fail(LDPC_EINVAL, "unknown out_dtype");
     if (B < 0) return fail(LDPC_EINVAL, "negative batch");
@@ -375,6 +377,13 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
     if (layered && early_stop == LDPC_ES_BATCH)
         return fail(LDPC_EINVAL, "layered min-sum has no batch-global stop (LDPC_ES_BATCH mirrors the reference's "
                                  "flooding classes): use LDPC_ES_OFF or LDPC_ES_FRAME");
+    if (half && early_stop == LDPC_ES_BATCH)
+        return fail(LDPC_EINVAL, "half-precision min-sum has no batch-global stop: use LDPC_ES_OFF or LDPC_ES_FRAME");
+    if (half) {
+        const uint32_t a = half_alpha_bits(alpha);  // 0 <= half(alpha) <= 1 (a NaN fails both)
+        if (!(a <= 0x3c00u || a == 0x8000u))
+            return fail(LDPC_EINVAL, "half-precision min-sum: alpha rounded to binary16 must be in [0, 1]");
+    }
     if (B == 0) return LDPC_OK;
     if (!d_llr || !d_bits) return fail(LDPC_EINVAL, "llr / bits is NULL");
     const bool streaming = use_stream(g, early_stop);
@@ -392,6 +401,20 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
         if (!g->lt.prog || layered_lds_bytes(g, early_stop) > kLdsMax)
             return fail(LDPC_EUNSUPPORTED, "layered min-sum: posteriors and messages of one wave's frames need " +
                                                std::to_string(layered_lds_bytes(g, early_stop)) + " bytes of LDS, above " +
+                                               std::to_string(kLdsMax));
+    }
+    if (half) {
+        // LDS-resident only; no partial sum may overflow binary16: 33 * 1024 < 65504
+        if (streaming)
+            return fail(LDPC_EUNSUPPORTED,
+                        "half-precision min-sum needs the LDS-resident schedule, and this graph decodes on the streaming "
+                        "kernels (lifting Z = " + std::to_string(g->Z) + (g->lds_ok ? "" : ", schedule encoding does not fit") +
+                        ", or LDPC_FLOOD_STREAM is set)");
+        if (g->max_dv > 32)
+            return fail(LDPC_EUNSUPPORTED, "half-precision min-sum: variable degree " + std::to_string(g->max_dv) + " above 32");
+        if (half_lds_bytes(g) > kLdsMax)
+            return fail(LDPC_EUNSUPPORTED, "half-precision min-sum: messages and ballots of one workgroup's frames need " +
+                                               std::to_string(half_lds_bytes(g)) + " bytes of LDS, above " +
                                                std::to_string(kLdsMax));
     }
     if (streaming && (g->max_dv > kStreamMaxDeg || g->max_dc > kStreamMaxDeg))
@@ -412,6 +435,7 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
                       d_work, s};
     if (layered_stream) return run_layered_stream(c);
     if (layered) return run_layered(c);
+    if (half) return run_half(c);
     if (streaming) return run_stream_decode(algo, c);
     return algo == LDPC_ALGO_MINSUM ? run_flood<LDPC_ALGO_MINSUM>(c) : run_flood<LDPC_ALGO_BP>(c);
 }

@@ -51,6 +51,13 @@ int run_layered(const FloodCall &c);
 // kStreamMaxDeg; c.es is LDPC_ES_OFF or LDPC_ES_FRAME).  c.work is the streaming workspace (stream_ws_bytes).
 int run_layered_stream(const FloodCall &c);
 
+// flood_half.hip: half-precision min-sum (LDPC_ALGO_MINSUM_F16; LDS-resident only, c.es is LDPC_ES_OFF or
+// LDPC_ES_FRAME, c.alpha already checked).  c.work holds the counter rows, one per 2 * FG frames: the head
+// of the flooding workspace of the same arguments.  half_alpha_bits: binary16 bits of half(alpha).
+size_t half_lds_bytes(const ldpc_graph *g);
+uint32_t half_alpha_bits(float alpha);
+int run_half(const FloodCall &c);
+
 // flood_stream.hip: the streaming decoders (messages in HBM, any graph)
 int64_t stream_ws_bytes(const ldpc_graph *g, int64_t B, int max_iter);
 int run_stream_decode(int algo, const FloodCall &c);

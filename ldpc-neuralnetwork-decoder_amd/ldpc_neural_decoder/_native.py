@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDPC_AMD_LIB", os.path.join(_HERE, "_lib", "libldpc_amd.so"))
 
 LDPC_ALGO_MINSUM, LDPC_ALGO_BP, LDPC_ALGO_LAYERED_MINSUM, LDPC_ALGO_LAYERED_MINSUM_ANY = 0, 1, 2, 3
+LDPC_ALGO_MINSUM_F16 = 5  # 4 is not assigned
 LDPC_ES_OFF, LDPC_ES_BATCH, LDPC_ES_FRAME = 0, 1, 2
 LDPC_OUT_U8, LDPC_OUT_F32 = 0, 1
 LDPC_GNN_EARLY_STOP = 1

@@ -117,10 +117,26 @@ class BeliefPropagationDecoder(_FloodDecoder):
 
 
 class MinSumScaledDecoder(_FloodDecoder):
-    """Scaled min-sum (traditional_decoders.py:137-285); c2v = prod sign * (alpha * min)."""
+    """Scaled min-sum (traditional_decoders.py:137-285); c2v = prod sign * (alpha * min).
+
+    ``precision="fp32"`` (the default) is the reference's decoder.  ``precision="fp16"`` (no reference
+    counterpart) runs the same flooding schedule on IEEE binary16 messages clamped to +-1024, two
+    frames per lane on packed f16 math (the algorithm is written out in include/ldpc_amd.h;
+    csrc/flood_half.hip).  It has no batch-global stop: ``early_stopping`` must be ``"frame"`` or
+    ``False``.  The LLRs stay float32; ``decode`` / ``decode_async``, ``out_dtype``, ``counters`` and
+    ``return_frame_iters`` are unchanged.  A graph without an LDS-resident schedule, or a variable
+    degree above 32, raises ``NativeError``."""
     _algo = N.LDPC_ALGO_MINSUM
 
-    def __init__(self, H, max_iterations=50, scaling_factor=0.75, early_stopping=True):
+    def __init__(self, H, max_iterations=50, scaling_factor=0.75, early_stopping=True, precision="fp32"):
+        if precision not in ("fp32", "fp16"):
+            raise ValueError(f'precision must be "fp32" or "fp16", got {precision!r}')
+        if precision == "fp16":
+            if early_stopping not in ("frame", False):
+                raise ValueError('precision="fp16" has no batch-global stop (early_stopping=True is the '
+                                 'reference\'s rule): pass early_stopping="frame" or False')
+            self._algo = N.LDPC_ALGO_MINSUM_F16
+        self.precision = precision
         self.scaling_factor = scaling_factor
         super().__init__(H, max_iterations, early_stopping)
 
