@@ -40,7 +40,8 @@ enum {
     LDPC_ALGO_BP = 1,
     LDPC_ALGO_LAYERED_MINSUM = 2,
     LDPC_ALGO_LAYERED_MINSUM_ANY = 3,
-    LDPC_ALGO_MINSUM_F16 = 5 /* 4 is not assigned: it stays an unknown value (LDPC_EINVAL) */
+    LDPC_ALGO_MINSUM_F16 = 5, /* 4 is not assigned: it stays an unknown value (LDPC_EINVAL) */
+    LDPC_ALGO_LAYERED_MINSUM_F16 = 6
 };
 enum { LDPC_ES_OFF = 0, LDPC_ES_BATCH = 1, LDPC_ES_FRAME = 2 };
 enum { LDPC_OUT_U8 = 0, LDPC_OUT_F32 = 1 };
@@ -176,7 +177,44 @@ int ldpc_graph_edges(const ldpc_graph *g, int32_t *h_edge_chk, int32_t *h_edge_v
  *     they mean for LDPC_ALGO_MINSUM.
  *   - Workspace.  ldpc_flood_workspace_size of the same arguments suffices.  It is required under the
  *     same conditions as for LDPC_ALGO_MINSUM.
- *   - ldpc_graph_set_variant has no effect on it: there is no compile-time schedule. */
+ *   - ldpc_graph_set_variant has no effect on it: there is no compile-time schedule.
+ *
+ * Half-precision layered min-sum (algo LDPC_ALGO_LAYERED_MINSUM_F16 = 6; no reference counterpart, this
+ * text is its definition).  Row-serial scaled min-sum on the Tanner graph.  Every value is IEEE binary16.
+ * Every operation is rounded to nearest-even with gradual underflow.  No multiply-add is fused.  C = 1024
+ * is the clamp.
+ *   Channel.   x[v] = clamp(half(llr[v]), -C, +C), as for LDPC_ALGO_MINSUM_F16: a magnitude that rounds to
+ *              infinity becomes +-C, so an infinite LLR is a defined input.
+ *   Scaling.   a = half(alpha).  Require 0 <= a <= 1, else LDPC_EINVAL.
+ *   Init.      app[v] = x[v].  c2v[e] = +0 for every edge (check-major order).
+ *   One iteration visits the checks in ascending index.  For check i with variables j_0 < ... < j_{d-1}:
+ *     1. t_k = clamp(app[j_k] - c2v[i,k], -C, +C).  For a variable of degree 1, t_k = x[j_k] exactly.
+ *     2. c2v[i,k] = (prod_{q != k} sgn t_q) * (a * min_{q != k} |t_q|).  sgn(0) = 0.  The product of signs
+ *        is formed first.  a * min is rounded once to binary16.  The minimum starts at C, not at +inf:
+ *        for d >= 2 that changes nothing, since every |t| <= C; a check of degree 1 therefore sends +a * C,
+ *        and nothing is ever infinite.
+ *     3. app[j_k] = t_k + c2v[i,k], unclamped.  For a degree-1 variable it is x + c2v, used for the
+ *        decision only.
+ *   Decision.  After each full iteration bit[v] = (app[v] < 0).
+ * |c2v| <= C and |t| <= C, so |app| <= 2 048 and |app - c2v| <= 3 072 < 65 504.  Nothing overflows, so
+ * there is no bail-out and no redo path (ldpc_flood_redo_count: LDPC_EUNSUPPORTED).
+ *   - The sign of a zero is not part of the contract.  `<`, abs and sgn cannot tell the two zeros apart,
+ *     and x + (+-0) differs only when x is itself a zero.  Decisions and iteration counts are defined,
+ *     message bits are not.
+ *   - NaN LLR.  That frame's outputs are 0 or 1 and otherwise unspecified.  Every other frame is
+ *     unaffected, the frame sharing its lanes included (the kernel packs two frames per lane).
+ *   - Early stop.  LDPC_ES_OFF and LDPC_ES_FRAME behave as for the other layered algorithms.
+ *     LDPC_ES_BATCH is LDPC_EINVAL.
+ *   - Graphs.  Every graph runs on streaming kernels of this algorithm's own, whatever lifting the library
+ *     detects.  LDPC_FLOOD_STREAM and ldpc_graph_set_variant have no effect.  A check or variable degree
+ *     above 32 is LDPC_EUNSUPPORTED.
+ *   - Outputs.  d_llr stays float32 (B, N).  d_bits, d_iters, d_batch_iters and d_counters mean what
+ *     they mean for the other layered algorithms.
+ *   - Workspace.  d_work of at least ldpc_layered_half_workspace_size(...) bytes is required, always:
+ *     posteriors and messages live there.  A missing or short one is LDPC_EINVAL.
+ *     ldpc_flood_workspace_size has no algo argument and sizes something else on an LDS-resident graph.
+ *     The query returns 0 for B = 0 or max_iter = 0, and LDPC_EINVAL for bad arguments. */
+int64_t ldpc_layered_half_workspace_size(const ldpc_graph *g, int64_t B, int max_iter, int early_stop);
 int64_t ldpc_flood_workspace_size(const ldpc_graph *g, int64_t B, int max_iter, int early_stop);
 int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_llr, int64_t B, int max_iter,
                       float alpha, int early_stop, int out_dtype, void *d_bits, int32_t *d_iters,

@@ -360,16 +360,24 @@ extern "C" int64_t ldpc_flood_workspace_size(const ldpc_graph *g, int64_t B, int
     return flood_ws(g, B, max_iter, early_stop, nullptr).bytes;
 }
 
+extern "C" int64_t ldpc_layered_half_workspace_size(const ldpc_graph *g, int64_t B, int max_iter, int early_stop) {
+    if (!g || B < 0 || max_iter < 0) return fail(LDPC_EINVAL, "bad arguments");
+    if (early_stop < 0 || early_stop > 2) return fail(LDPC_EINVAL, "unknown early_stop mode");
+    if (B == 0 || max_iter == 0) return 0;
+    return layered_half_ws_bytes(g, B);
+}
+
 extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_llr, int64_t B,
                                  int max_iter, float alpha, int early_stop, int out_dtype,
                                  void *d_bits, int32_t *d_iters, int32_t *d_batch_iters,
                                  uint64_t *d_counters, void *d_work, int64_t work_bytes, void *stream) {
     if (!g) return fail(LDPC_EINVAL, "graph is NULL");
     if (algo != LDPC_ALGO_MINSUM && algo != LDPC_ALGO_BP && algo != LDPC_ALGO_LAYERED_MINSUM &&
-        algo != LDPC_ALGO_LAYERED_MINSUM_ANY && algo != LDPC_ALGO_MINSUM_F16)
+        algo != LDPC_ALGO_LAYERED_MINSUM_ANY && algo != LDPC_ALGO_MINSUM_F16 && algo != LDPC_ALGO_LAYERED_MINSUM_F16)
         return fail(LDPC_EINVAL, "unknown algo");
     const bool layered = algo == LDPC_ALGO_LAYERED_MINSUM || algo == LDPC_ALGO_LAYERED_MINSUM_ANY;
     const bool half = algo == LDPC_ALGO_MINSUM_F16;
+    const bool layered_half = algo == LDPC_ALGO_LAYERED_MINSUM_F16;
     if (early_stop < 0 || early_stop > 2) return fail(LDPC_EINVAL, "unknown early_stop mode");
     if (out_dtype != LDPC_OUT_U8 && out_dtype != LDPC_OUT_F32) return fail(LDPC_EINVAL, "unknown out_dtype");
     if (B < 0) return fail(LDPC_EINVAL, "negative batch");
@@ -379,13 +387,32 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
                                  "flooding classes): use LDPC_ES_OFF or LDPC_ES_FRAME");
     if (half && early_stop == LDPC_ES_BATCH)
         return fail(LDPC_EINVAL, "half-precision min-sum has no batch-global stop: use LDPC_ES_OFF or LDPC_ES_FRAME");
-    if (half) {
+    if (layered_half && early_stop == LDPC_ES_BATCH)
+        return fail(LDPC_EINVAL, "half-precision layered min-sum has no batch-global stop: use LDPC_ES_OFF or "
+                                 "LDPC_ES_FRAME");
+    if (half || layered_half) {
         const uint32_t a = half_alpha_bits(alpha);  // 0 <= half(alpha) <= 1 (a NaN fails both)
         if (!(a <= 0x3c00u || a == 0x8000u))
             return fail(LDPC_EINVAL, "half-precision min-sum: alpha rounded to binary16 must be in [0, 1]");
     }
     if (B == 0) return LDPC_OK;
     if (!d_llr || !d_bits) return fail(LDPC_EINVAL, "llr / bits is NULL");
+    if (layered_half) {
+        // streaming kernels of its own on every graph: neither LDPC_FLOOD_STREAM nor the variant matters
+        if (g->max_dv > kStreamMaxDeg || g->max_dc > kStreamMaxDeg)
+            return fail(LDPC_EUNSUPPORTED, "half-precision layered min-sum: node degree above " + std::to_string(kStreamMaxDeg));
+        const int64_t need = layered_half_ws_bytes(g, B);
+        if (!d_work || work_bytes < need)
+            return fail(LDPC_EINVAL, "workspace too small: need " + std::to_string(need) +
+                                         " bytes (ldpc_layered_half_workspace_size)");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (d_batch_iters && early_stop == LDPC_ES_OFF) {
+            hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(1), 0, s, d_batch_iters, max_iter);
+            LDPC_CHECK_LAUNCH("fill");
+        }
+        return run_layered_stream_half(FloodCall{g, d_llr, B, max_iter, alpha, early_stop, out_dtype, d_bits, d_iters,
+                                                 d_counters, d_batch_iters, d_work, s});
+    }
     const bool streaming = use_stream(g, early_stop);
     // LDPC_ALGO_LAYERED_MINSUM_ANY on a streaming graph: the streaming layered decoder, one launch per layer
     // segment (flood_layered_stream.hip); elsewhere it is LDPC_ALGO_LAYERED_MINSUM, refusals included (the

@@ -58,6 +58,12 @@ size_t half_lds_bytes(const ldpc_graph *g);
 uint32_t half_alpha_bits(float alpha);
 int run_half(const FloodCall &c);
 
+// flood_layered_stream_half.hip: half-precision layered min-sum (LDPC_ALGO_LAYERED_MINSUM_F16) on streaming
+// kernels of its own, any graph with node degrees up to kStreamMaxDeg; c.es is LDPC_ES_OFF or LDPC_ES_FRAME,
+// c.alpha already checked.  c.work holds layered_half_ws_bytes(g, B) bytes, always.
+int64_t layered_half_ws_bytes(const ldpc_graph *g, int64_t B);
+int run_layered_stream_half(const FloodCall &c);
+
 // flood_stream.hip: the streaming decoders (messages in HBM, any graph)
 int64_t stream_ws_bytes(const ldpc_graph *g, int64_t B, int max_iter);
 int run_stream_decode(int algo, const FloodCall &c);

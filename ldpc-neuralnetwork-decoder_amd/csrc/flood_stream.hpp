@@ -1,5 +1,6 @@
 // flood_stream.hpp -- what the streaming translation units share: flood_stream.hip (flooding and hybrid
-// min-sum) and flood_layered_stream.hip (layered min-sum).  The layout is flood_stream.hip's: every
+// min-sum), flood_layered_stream.hip (layered min-sum) and flood_layered_stream_half.hip (its binary16
+// form, which borrows the syndrome and emit passes only).  The layout is flood_stream.hip's: every
 // array frame-fastest, so that a wave -- 64 consecutive frames of one node -- loads and stores 256
 // contiguous bytes.
 #pragma once

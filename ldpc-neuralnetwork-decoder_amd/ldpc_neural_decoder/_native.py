@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("LDPC_AMD_LIB", os.path.join(_HERE, "_lib", "libldpc_a
 
 LDPC_ALGO_MINSUM, LDPC_ALGO_BP, LDPC_ALGO_LAYERED_MINSUM, LDPC_ALGO_LAYERED_MINSUM_ANY = 0, 1, 2, 3
 LDPC_ALGO_MINSUM_F16 = 5  # 4 is not assigned
+LDPC_ALGO_LAYERED_MINSUM_F16 = 6
 LDPC_ES_OFF, LDPC_ES_BATCH, LDPC_ES_FRAME = 0, 1, 2
 LDPC_OUT_U8, LDPC_OUT_F32 = 0, 1
 LDPC_GNN_EARLY_STOP = 1
@@ -36,6 +37,7 @@ SIGNATURES = {
     "ldpc_graph_edges": (ctypes.c_int, [_P, _P, _P]),
     "ldpc_graph_set_variant": (ctypes.c_int, [_P, ctypes.c_int]),
     "ldpc_flood_workspace_size": (_I64, [_P, _I64, ctypes.c_int, ctypes.c_int]),
+    "ldpc_layered_half_workspace_size": (_I64, [_P, _I64, ctypes.c_int, ctypes.c_int]),
     "ldpc_custom_minsum_workspace_size": (_I64, [_P, _I64]),
     "ldpc_gnn_custom_var_workspace_size": (_I64, [_P, ctypes.c_int, ctypes.c_int, _I64, ctypes.c_int]),
     "ldpc_gnn_custom_var_forward": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,

@@ -54,6 +54,10 @@ class _FloodDecoder:
     def _alpha(self):
         return 0.0
 
+    def _workspace_size(self, g, B, es):
+        """Bytes of scratch the decode needs (a class whose algo has a query of its own overrides this)."""
+        return N.lib().ldpc_flood_workspace_size(g.handle, B, self.max_iterations, es)
+
     def decode(self, llr, out_dtype=torch.float32, counters=None, return_frame_iters=False):
         """llr (B, N) float32 -> (decoded_bits (B, N) float32 0/1, iterations: int).
 
@@ -85,7 +89,7 @@ class _FloodDecoder:
         kind = N.LDPC_OUT_F32 if out_dtype == torch.float32 else N.LDPC_OUT_U8
         batch_iters = torch.zeros(1, dtype=torch.int32, device=dev)
         frame_iters = torch.empty(B, dtype=torch.int32, device=dev) if return_frame_iters else None
-        wsb = N.check(N.lib().ldpc_flood_workspace_size(g.handle, B, self.max_iterations, es))
+        wsb = N.check(self._workspace_size(g, B, es))
         ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
         N.check(N.lib().ldpc_flood_decode(
             g.handle, self._algo, N.ptr(x), B, int(self.max_iterations), float(self._alpha()), es,
@@ -160,13 +164,26 @@ class LayeredMinSumDecoder(_FloodDecoder):
     kernels (csrc/flood_layered_stream.hip: posteriors and messages in device memory, one launch per
     run of variable-disjoint checks and check degree), with the same decisions and iteration counts,
     bit for bit; a graph that has an LDS-resident schedule runs exactly what the default runs.  Node
-    degrees above 32 raise ``NativeError`` on the streaming kernels, as for the flooding classes."""
+    degrees above 32 raise ``NativeError`` on the streaming kernels, as for the flooding classes.
+
+    ``precision="fp16"`` runs the same schedule on IEEE binary16 posteriors and messages clamped to
+    +-1024 (the algorithm is written out in include/ldpc_amd.h, "Half-precision layered min-sum";
+    csrc/flood_layered_stream_half.hip): streaming kernels of its own on EVERY graph, two frames per
+    lane on packed f16 math, half the bytes per edge and iteration.  ``any_graph`` is then accepted and
+    has no effect.  The LLRs stay float32; everything else above is unchanged.  ``precision="fp32"``
+    (the default) is the float32 decoder described above."""
     _algo = N.LDPC_ALGO_LAYERED_MINSUM
 
-    def __init__(self, H, max_iterations=50, scaling_factor=0.75, early_stopping=True, any_graph=False):
+    def __init__(self, H, max_iterations=50, scaling_factor=0.75, early_stopping=True, any_graph=False,
+                 precision="fp32"):
+        if precision not in ("fp32", "fp16"):
+            raise ValueError(f'precision must be "fp32" or "fp16", got {precision!r}')
         self.scaling_factor = scaling_factor
         self.any_graph = bool(any_graph)
-        if self.any_graph:
+        self.precision = precision
+        if precision == "fp16":
+            self._algo = N.LDPC_ALGO_LAYERED_MINSUM_F16
+        elif self.any_graph:
             self._algo = N.LDPC_ALGO_LAYERED_MINSUM_ANY
         super().__init__(H, max_iterations, early_stopping)
 
@@ -175,3 +192,8 @@ class LayeredMinSumDecoder(_FloodDecoder):
 
     def _es_mode(self):
         return N.LDPC_ES_FRAME if self.early_stopping else N.LDPC_ES_OFF
+
+    def _workspace_size(self, g, B, es):
+        if self.precision == "fp16":
+            return N.lib().ldpc_layered_half_workspace_size(g.handle, B, self.max_iterations, es)
+        return super()._workspace_size(g, B, es)
