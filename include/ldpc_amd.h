@@ -529,6 +529,54 @@ int ldpc_index_rows_minsum(const float *d_x, int64_t B, int64_t E_in, const int6
 int ldpc_index_rows_varsum(const float *d_llr, int64_t B, int64_t N_var, const float *d_c2v, int64_t E_in,
                            const int64_t *d_rows, int64_t R, int W, int damp, float *d_out, void *stream);
 
+/* ---- neural min-sum decoder, fused inference (LDPCNeuralDecoder.forward, models/decoder.py) ----
+ * One kernel runs every iteration of a frame with its messages in LDS; HBM sees the LLRs, the weights
+ * and the output.  The result is DEFINED as the operation sequence of LDPCNeuralDecoder.forward as the
+ * layer kernels above evaluate it -- float32 throughout, no multiply-add fused, every sum in the stated
+ * order -- so it equals the layer path's output bit for bit:
+ *   x0[e]  = +0.0f + llr[var(e)]   (ldpc_gather_sum's sequence on a one-entry row: -0.0 becomes +0.0)
+ *   v_{-1} = x0
+ *   for l = 0 .. I - 1:
+ *     c_l[e] = ldpc_check_groups_minsum's rule on v_{l-1}: prod sign(v + 1e-10f) * min |v|' over the
+ *              other edges of e's check, |0| -> 1e10, the minimum capped at 1e10 when the check has
+ *              padding (K > degree - 1), NaN if another edge is NaN, the sign of a zero product kept
+ *              (the same device function, csrc/check_group.hpp, serves both paths)
+ *     for l < I - 1:
+ *       S[e]   = ldpc_var_groups_sum's sequence: start at +0.0f, add the c_l of the variable's other
+ *                edges in ascending order, skipping e
+ *       r      = x0[e] * w_ch_l[e];  r = r + S[e];
+ *       r      = r + w_res_l[i] * v_{l-1-i}[e]   for i = 0 .. min(l, depth_L) - 1, in this order
+ *       v_l[e] = r
+ *   app[j] = +0.0f + the c_{I-1} of variable j's edges, ascending
+ *   soft   = 1.0f / (1.0f + expf(-((-app) + (-llr))))      ldpc_output_layer on (-app, -llr)
+ * Non-finite inputs propagate exactly as through the layers; frames are independent.
+ *
+ * Graph description: the var-major edge numbering of create_LLR_mapping in the group form of the layer
+ * kernels.  h_cptr (G + 1) / h_cmem (E): each check's edges, ascending inside a check; h_vptr (N + 1):
+ * variable j's edges are the run [vptr[j], vptr[j + 1]); K: the row length of the check index tensor.
+ * ldpc_neural_plan_create validates on the host (cmem a permutation of 0 .. E - 1, cptr and vptr
+ * monotone and tiling [0, E), E < 65536: else LDPC_EINVAL; LDPC_EUNSUPPORTED when no depth_L could
+ * run, see below), uploads the 16-bit tables to the current device once, and synchronises.
+ * ldpc_neural_layout touches no device: the same validation, then the kernel's frames per workgroup
+ * (as many as fit beside the tables, at most 8), threads per workgroup and LDS bytes for depth_L (any
+ * output may be NULL).  LDPC_EUNSUPPORTED when depth_L > 8, when N or G exceeds 65535, or when one
+ * frame (the LLR row, one c row and max(depth_L, 1) v rows) does not fit 160 KB beside the tables.
+ * ldpc_neural_forward decides through the same function, so the two cannot disagree.
+ * ldpc_neural_forward: asynchronous on `stream`, no workspace, no allocation.  d_w_ch (I - 1, E) and
+ * d_w_res (I - 1, depth_L) float32 row-major (iterations == 1: no variable layer, both may be NULL;
+ * depth_L == 0: d_w_res may be NULL); d_llr (B, N) rows contiguous, any 4-byte-aligned base; at least
+ * one of d_app (B, N) and d_soft (B, N) must be given.  iterations >= 1; B == 0 launches nothing. */
+typedef struct ldpc_neural_plan ldpc_neural_plan;
+int ldpc_neural_plan_create(int N, int G, int64_t E, const int32_t *h_cptr, const int32_t *h_cmem,
+                            const int32_t *h_vptr, int K, ldpc_neural_plan **out);
+int ldpc_neural_plan_destroy(ldpc_neural_plan *p);
+int ldpc_neural_layout(int N, int G, int64_t E, const int32_t *h_cptr, const int32_t *h_cmem,
+                       const int32_t *h_vptr, int K, int depth_L, int *frames, int *threads,
+                       int64_t *lds_bytes);
+int ldpc_neural_forward(const ldpc_neural_plan *p, int iterations, int depth_L, const float *d_w_ch,
+                        const float *d_w_res, const float *d_llr, int64_t B, float *d_app, float *d_soft,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,11 @@ SIGNATURES = {
     "ldpc_gnn_backward_ds_ex2": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
                                                 ctypes.c_int, _I64, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int, _P, _I64,
                                                 _P]),
+    "ldpc_neural_plan_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _I64, _P, _P, _P, ctypes.c_int, _P]),
+    "ldpc_neural_plan_destroy": (ctypes.c_int, [_P]),
+    "ldpc_neural_layout": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _I64, _P, _P, _P, ctypes.c_int, ctypes.c_int,
+                                          _P, _P, _P]),
+    "ldpc_neural_forward": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _I64, _P, _P, _P]),
 }
 
 _lib = None
@@ -259,5 +264,72 @@ class NativeGnnPlan:
         if h and _lib is not None:
             try:
                 _lib.ldpc_gnn_plan_destroy(h)
+            except Exception:
+                pass
+
+
+def neural_layout(cptr, cmem, vptr, K, depth_L):
+    """ldpc_neural_layout on host arrays (no device touched): (frames per workgroup, threads per
+    workgroup, LDS bytes) of the fused neural min-sum kernel, or None when the library answers
+    LDPC_EUNSUPPORTED (depth_L > 8, or one frame does not fit LDS).  Anything else raises."""
+    import numpy as np
+    cp, cm, vp = (np.ascontiguousarray(a, dtype=np.int32) for a in (cptr, cmem, vptr))
+    F, T, L = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    rc = lib().ldpc_neural_layout(len(vp) - 1, len(cp) - 1, len(cm), cp.ctypes.data_as(_P), cm.ctypes.data_as(_P),
+                                  vp.ctypes.data_as(_P), int(K), int(depth_L), ctypes.byref(F), ctypes.byref(T),
+                                  ctypes.byref(L))
+    if rc == LDPC_EUNSUPPORTED:
+        return None
+    check(rc)
+    return F.value, T.value, L.value
+
+
+class NativeNeuralPlan:
+    """An ldpc_neural_plan* on one device: the check lists and variable runs of the E var-major LLR
+    indices (cptr (G + 1), cmem (E), vptr (N + 1) host arrays; K = the check index tensor's row
+    length), uploaded once as the fused kernel's 16-bit tables."""
+
+    def __init__(self, cptr, cmem, vptr, K, device):
+        import numpy as np
+        cp, cm, vp = (np.ascontiguousarray(a, dtype=np.int32) for a in (cptr, cmem, vptr))
+        self.N, self.G, self.E, self.K, self.device = len(vp) - 1, len(cp) - 1, len(cm), int(K), device
+        self._tables, self._layouts = (cp, cm, vp), {}
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            check(lib().ldpc_neural_plan_create(self.N, self.G, self.E, cp.ctypes.data_as(_P), cm.ctypes.data_as(_P),
+                                                vp.ctypes.data_as(_P), self.K, ctypes.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def layout(self, depth_L):
+        """(frames, threads, LDS bytes) for depth_L, or None (see neural_layout)."""
+        if depth_L not in self._layouts:
+            self._layouts[depth_L] = neural_layout(*self._tables, self.K, depth_L)
+        return self._layouts[depth_L]
+
+    def forward(self, iterations, depth_L, w_ch, w_res, llr, app=None, soft=None):
+        """ldpc_neural_forward on llr's device and current stream.  llr (B, N) float32 with contiguous
+        rows; w_ch (I - 1, E) / w_res (I - 1, depth_L) contiguous float32 (None when iterations == 1)."""
+        B, n = llr.shape
+        if n != self.N or llr.dtype != torch.float32 or not llr.is_contiguous():
+            raise NativeError(f"llr must be contiguous float32 (B, {self.N})")
+        if iterations > 1:
+            for t, shape in ((w_ch, (iterations - 1, self.E)), (w_res, (iterations - 1, depth_L))):
+                if t is None or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise NativeError(f"weights must be contiguous float32 of shape {shape}")
+        for t in (app, soft):
+            if t is not None and (tuple(t.shape) != (B, n) or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise NativeError(f"outputs must be contiguous float32 ({B}, {n})")
+        with torch.cuda.device(llr.device):
+            check(lib().ldpc_neural_forward(self._h, int(iterations), int(depth_L), ptr(w_ch), ptr(w_res), ptr(llr),
+                                            B, ptr(app), ptr(soft), stream_ptr(llr.device)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            try:
+                _lib.ldpc_neural_plan_destroy(h)
             except Exception:
                 pass

@@ -27,15 +27,28 @@ The sign: the channel's LLR is log P(0)/P(1) (channel.py:127-148), so P(bit = 1)
 sigmoid(-LLR); the negation is explicit here rather than left to training (MessageGNN keeps the
 reference's sigmoid(+LLR), message_gnn_decoder.py:307).  Every gather, min-sum, sum, residual
 and output op runs in csrc/layers.hip; there is no CPU path.
+
+Inference takes one fused kernel instead (csrc/neural_ms.hip, ``ldpc_neural_forward``): when no
+gradient can be asked for (grad mode off, or neither ``llrs`` nor any parameter requires grad), both
+index tensors have create_LLR_mapping's group structure and a frame's messages fit one CU's LDS,
+every iteration of a frame runs inside that kernel with its messages in LDS.  It evaluates exactly the
+layer kernels' float32 operation sequence, so ``soft`` (and, with ``ground_truth``, the loss, which
+the output layer still computes from the kernel's ``app``) is the layer path's bit for bit.  Anything
+else -- training, ragged or non-group index tensors, E >= 65536, depth_L > 8, frames too large for
+LDS -- runs the layers as before.  ``decoder.use_fused = False`` or ``LDPC_NEURAL_FUSED=0`` in the
+environment force the layer path.
 """
+import os
+
 import torch
 import torch.nn as nn
 
 from ldpc_neural_decoder import _native as N
 from ldpc_neural_decoder.models.layers import (
-    OutputLayer, ResidualLayer, _check_index, check_minsum, gather_sum)
+    OutputLayer, ResidualLayer, _check_groups, _check_index, _var_groups, check_minsum, gather_sum)
 
 _STRUCT = {}
+_PLANS = {}  # (index tensor identities and versions, device) -> NativeNeuralPlan, or None (no group structure)
 
 
 def edge_variables(var_index_tensor):
@@ -75,6 +88,27 @@ def _structure(var_index_tensor, n_vars, dev):
     return prepared
 
 
+def _fused_plan(check_index_tensor, var_index_tensor, cidx, vidx, E, dev):
+    """The fused kernel's plan for this pair of index tensors, or None when either lacks the group
+    structure (or E needs more than 16-bit indices); cached per pair, keyed as _structure keys."""
+    ct, vt = torch.as_tensor(check_index_tensor), torch.as_tensor(var_index_tensor)
+    key = (id(ct), ct.data_ptr(), ct._version, id(vt), vt.data_ptr(), vt._version, str(dev))
+    hit = _PLANS.get(key)
+    if hit is not None and hit[0] is ct and hit[1] is vt:
+        return hit[2]
+    plan = None
+    if 0 < E < 65536:
+        cg, vptr = _check_groups(cidx, E), _var_groups(vidx, E)
+        if cg is not None and vptr is not None:
+            tables = (cg[0].cpu().numpy(), cg[1].cpu().numpy(), vptr.cpu().numpy(), cidx.shape[0])
+            if N.neural_layout(*tables, 0) is not None:  # else no depth_L fits LDS: no plan, the layers run
+                plan = N.NativeNeuralPlan(*tables, dev)
+    if len(_PLANS) > 8:
+        _PLANS.clear()
+    _PLANS[key] = (ct, vt, plan)
+    return plan
+
+
 class LDPCNeuralDecoder(nn.Module):
     """Neural min-sum decoder with channel and residual weights (see module docstring)."""
 
@@ -88,6 +122,39 @@ class LDPCNeuralDecoder(nn.Module):
         self.residual_layers = nn.ModuleList([ResidualLayer(num_nodes, depth_L)
                                               for _ in range(num_iterations - 1)])
         self.output_layer = OutputLayer()
+        self.use_fused = True  # False: always the layer path (LDPC_NEURAL_FUSED=0 does the same)
+        self._fused_w = (None, None, None)  # key, stacked w_ch (I - 1, E), stacked w_res (I - 1, depth_L)
+
+    def _fused_weights(self, dev):
+        """The residual layers' weights stacked for ldpc_neural_forward, rebuilt when a parameter's
+        storage or version changes (an optimizer step, load_state_dict, an in-place edit)."""
+        if not len(self.residual_layers):
+            return None, None
+        params = [p for res in self.residual_layers for p in (res.w_ch, res.w_res)]
+        key = (str(dev),) + tuple((p.data_ptr(), p._version) for p in params)
+        if key != self._fused_w[0]:
+            stack = lambda ws: torch.stack([w.detach().to(dev, torch.float32) for w in ws]).contiguous()
+            self._fused_w = (key, stack([res.w_ch for res in self.residual_layers]),
+                             stack([res.w_res for res in self.residual_layers]))
+        return self._fused_w[1], self._fused_w[2]
+
+    def _fused(self, llr, check_index_tensor, var_index_tensor, cidx, vidx, want_app):
+        """soft (or app, for the output layer's loss) from the fused kernel, or None when this call
+        has to run the layers."""
+        if not self.use_fused or os.environ.get("LDPC_NEURAL_FUSED", "1") == "0":
+            return None
+        if torch.is_grad_enabled() and (llr.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return None
+        if not llr.shape[0]:
+            return None
+        plan = _fused_plan(check_index_tensor, var_index_tensor, cidx, vidx, self.num_nodes, llr.device)
+        if plan is None or plan.layout(self.depth_L) is None:
+            return None
+        w_ch, w_res = self._fused_weights(llr.device)
+        out = torch.empty_like(llr)
+        plan.forward(self.num_iterations, self.depth_L, w_ch, w_res, llr,
+                     app=out if want_app else None, soft=None if want_app else out)
+        return out
 
     def forward(self, llrs, check_index_tensor, var_index_tensor, ground_truth=None):
         home = llrs.device
@@ -100,6 +167,13 @@ class LDPCNeuralDecoder(nn.Module):
             raise RuntimeError(f"index tensors describe {E} LLR indices, decoder built for {self.num_nodes}")
         cidx = _check_index(check_index_tensor, E, dev)
         vidx = _check_index(var_index_tensor, E, dev, compact=True)
+        gt = None if ground_truth is None else ground_truth.to(dev, torch.float32)
+        fused = self._fused(llr, check_index_tensor, var_index_tensor, cidx, vidx, want_app=gt is not None)
+        if fused is not None:
+            if gt is None:
+                return fused.to(home), None
+            soft, loss = self.output_layer(-fused, -llr, gt)
+            return soft.to(home), loss.to(home)
         x0 = gather_sum(llr, x0_idx)
         v, prevs = x0, []
         for res in self.residual_layers:
@@ -107,7 +181,6 @@ class LDPCNeuralDecoder(nn.Module):
             v = res(x0, gather_sum(c, vidx), prevs)
             prevs = [v] + prevs[:max(self.depth_L - 1, 0)]
         app = gather_sum(check_minsum(v, cidx), app_idx)
-        gt = None if ground_truth is None else ground_truth.to(dev, torch.float32)
         soft, loss = self.output_layer(-app, -llr, gt)
         if loss is None:
             return soft.to(home), None
