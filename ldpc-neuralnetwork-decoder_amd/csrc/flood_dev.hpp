@@ -343,7 +343,8 @@ struct Ctx {
     float alpha;
     int out_dtype;
     void *bits;
-    bool direct_bits;  // mode 0, final iteration: write decisions straight to HBM
+    bool direct_bits;  // mode 0, final iteration: write decisions straight to HBM (flood_kernel; the
+                       // fixed kernel's bodies take it as a template parameter, DIRECT)
     bool ballots;      // ES: record decisions as ballots
 };
 
@@ -356,7 +357,20 @@ __device__ __forceinline__ uint64_t seg_rotl(uint64_t w, int s, int z, uint64_t 
     return ((w & low) << s) | ((w & ~low) >> (z - s));
 }
 
-// decision of variable (col, (k + s) mod Z) computed on the lane of check row k
+// the decisions of column col as a ballot word: bit f*Z + t is variable t of frame f
+__device__ __forceinline__ void var_ballot(const Ctx &C, const Lane &L, int col, int bit) {
+    const uint64_t w = __ballot(bit);
+    if (L.lane == 0) C.words[col] = w;
+}
+// the same from the lanes of check row k, where lane f*Z + k holds variable (k + s) mod Z: rotate
+// every Z-bit segment of the ballot left by s (uniform, scalar) so that bit f*Z + t is variable t
+__device__ __forceinline__ void ext_ballot(const Ctx &C, const Lane &L, int col, int s4, int bit) {
+    const uint64_t w = seg_rotl(__ballot(bit), s4 >> 2, C.T.Z, C.T.rep1);
+    if (L.lane == 0) C.words[col] = w;
+}
+
+// decision of variable (col, (k + s) mod Z) computed on the lane of check row k (the table-driven
+// kernel's form; the fixed kernel stores through FixedBody's DecOut)
 __device__ __forceinline__ void ext_decision(const Ctx &C, const Lane &L, int col, int s4, float app,
                                              int &errs) {
     const int bit = app < 0.0f;  // NaN < 0 is false -> 0 (traditional_decoders.py:252)
@@ -369,12 +383,7 @@ __device__ __forceinline__ void ext_decision(const Ctx &C, const Lane &L, int co
         put_bit(C.bits, C.out_dtype, fr * C.T.N + (col * L.z4 + ((k4 + s4) & L.zmask4)) / 4, bit);
         errs += bit;
     }
-    if (C.ballots) {
-        // lane f*Z + k holds variable (k + s) mod Z: rotate every Z-bit segment of the ballot left
-        // by s (uniform, scalar) so that bit f*Z + t is variable t, as in var_decision
-        const uint64_t w = seg_rotl(__ballot(bit), s4 >> 2, C.T.Z, C.T.rep1);
-        if (L.lane == 0) C.words[col] = w;
-    }
+    if (C.ballots) ext_ballot(C, L, col, s4, bit);
 }
 
 __device__ __forceinline__ void var_decision(const Ctx &C, const Lane &L, int col, float app, int &errs) {
@@ -386,10 +395,7 @@ __device__ __forceinline__ void var_decision(const Ctx &C, const Lane &L, int co
         put_bit(C.bits, C.out_dtype, fr * C.T.N + (int64_t)col * L.Z() + k, bit);
         errs += bit;
     }
-    if (C.ballots) {
-        const uint64_t w = __ballot(bit);
-        if (L.lane == 0) C.words[col] = w;
-    }
+    if (C.ballots) var_ballot(C, L, col, bit);
 }
 
 // ---------------------------------------------------------------- check node update
@@ -753,47 +759,72 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
     int my_iters = max_iter;
     uint64_t done = 0;
     constexpr bool kEvery = ES == LDPC_ES_BATCH || ES == LDPC_ES_FRAME || ES == ES_P1;  // ballots every iteration
-    for (int it = 0; it < max_iter; ++it) {
-        const bool last = it == max_iter - 1;
-        C.direct_bits = (ES == LDPC_ES_OFF || ES == ES_P2) && last;
-        C.ballots = ES == LDPC_ES_BATCH || ES == LDPC_ES_FRAME || ES == ES_P1 || (ES == ES_P2 && last);
+    // One iteration.  ES_OFF and ES_P2 take decisions in the last iteration only: where the body
+    // asks for it (Body::kPeel) their loop runs the iterations before it (WHEN 0: no decision code,
+    // no store to global memory, ballots and direct_bits constant) and the last one follows the
+    // loop as straight code (WHEN 1: decisions stored directly, DIRECT, and no v2c written).
+    // Otherwise one loop holds both forms (WHEN 2: `last` is a run-time value); the modes that
+    // take decisions, as ballots, in every iteration always do.  The barriers of an iteration are
+    // the same in every form.
+    // -> kGoOn, kStop (early stop: leave the loop) or kLeft (bail-out: the workgroup has left the decode)
+    constexpr int kGoOn = 0, kStop = 1, kLeft = 2;
+    constexpr bool kPeel = !kEvery && Body::kPeel;
+    auto iteration = [&](auto when, int it) __attribute__((always_inline)) -> int {
+        constexpr int WHEN = decltype(when)::value;
+        static_assert(kPeel ? WHEN < 2 : WHEN == 2, "the last iteration is peeled or it is not");
+        const bool last = WHEN == 2 ? it == max_iter - 1 : WHEN == 1;
+        constexpr bool DIRECT = WHEN == 1;
+        C.direct_bits = !kEvery && last;
+        C.ballots = kEvery || (ES == ES_P2 && last);
         if constexpr (Body::kBail) {
             // Bail-out instances hold the fast check update only.  The sticky flag (a non-finite
             // LLR or APP: a message may be NaN) is read here by every wave after a barrier and
             // written only between the next two, so the branch is workgroup-uniform: the group is
             // appended to the redo list and decoded again, from its LLRs, by flood_redo_kernel.
             // Whatever this workgroup has emitted so far is rewritten there; no counter row yet.
-            if (__builtin_amdgcn_readfirstlane(*C.flag) != 0) {
+            if (__builtin_expect(__builtin_amdgcn_readfirstlane(*C.flag) != 0, 0)) {
                 if (tid == 0) C.redo[1 + atomicAdd(C.redo, 1u)] = (uint32_t)L.group;
-                return;
+                return kLeft;
             }
         }
         // decisions are taken only in the iterations that need them (DEC = true), so the other
         // iterations carry no decision code at all
-        if (kEvery || last)
-            body.template check<true>(C, L, errs);
-        else
-            body.template check<false>(C, L, errs);
+        if constexpr (WHEN == 0) {
+            body.template check<false, false>(C, L, errs);
+        } else if constexpr (WHEN == 1 || kEvery) {
+            body.template check<true, DIRECT>(C, L, errs);
+        } else {
+            if (last)
+                body.template check<true, false>(C, L, errs);
+            else
+                body.template check<false, false>(C, L, errs);
+        }
         mark(1 + 4 * it);
         __syncthreads();
         mark(2 + 4 * it);
         if (C.ballots && tid == 0) C.words[Nb] = 0;
-        if (last)
-            body.template var<true, false>(C, L, errs);
-        else if (kEvery)
-            body.template var<true, true>(C, L, errs);
-        else
-            body.template var<false, true>(C, L, errs);
+        if constexpr (WHEN == 0) {
+            body.template var<false, true, false>(C, L, errs);
+        } else if constexpr (WHEN == 1) {
+            body.template var<true, false, DIRECT>(C, L, errs);
+        } else {
+            if (last)
+                body.template var<true, false, false>(C, L, errs);
+            else if (kEvery)
+                body.template var<true, true, false>(C, L, errs);
+            else
+                body.template var<false, true, false>(C, L, errs);
+        }
         mark(3 + 4 * it);
         __syncthreads();
         mark(4 + 4 * it);
+        bool stop = false;
         if (C.ballots) {
             // syndrome H x = 0 per frame (traditional_decoders.py:111-134), from the ballots
             const uint64_t m = __ballot(body.parity(C, L));
             if (L.lane == 0 && m) atomicOr((unsigned long long *)&C.words[Nb], (unsigned long long)m);
             __syncthreads();
             const uint64_t vmask = frame_valid_mask(C.words[Nb], Z, FG) & exist;
-            bool stop = false;
             if constexpr (ES == LDPC_ES_BATCH) {
                 if (L.valid && L.k == 0 && ((vmask >> L.f) & 1ull))
                     W.valid[L.frame * W.nvw + (it >> 5)] |= 1u << (it & 31);
@@ -822,8 +853,19 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
                 if (vmask != exist && tid == 0) atomicOr(&W.ctl[1], 1);
             }
             __syncthreads();
-            if (stop) break;
         }
+        return stop ? kStop : kGoOn;
+    };
+    if constexpr (!kPeel) {
+        for (int it = 0; it < max_iter; ++it) {
+            const int r = iteration(ic<2>{}, it);
+            if (r == kLeft) return;
+            if (r == kStop) break;
+        }
+    } else {
+        for (int it = 0; it < max_iter - 1; ++it)
+            if (iteration(ic<0>{}, it) == kLeft) return;
+        if (max_iter > 0 && iteration(ic<1>{}, max_iter - 1) == kLeft) return;
     }
     if constexpr (ES == LDPC_ES_FRAME) {
         const uint64_t rest = exist & ~done;
@@ -844,11 +886,13 @@ __device__ __forceinline__ void flood_drive(Body &body, Ctx &C, const Lane &L, i
 template <int ALGO>
 struct GenericBody {
     static constexpr bool kBail = false;  // its check update handles every value
+    static constexpr bool kPeel = false;  // one loop: decisions are a run-time matter here (C.direct_bits)
     int wave;
     __device__ __forceinline__ void init(Ctx &C, const Lane &L) { init_phase(C, L, wave); }
-    template <bool DEC>
+    // DEC, DIRECT: this body reads C.direct_bits / C.ballots at run time instead
+    template <bool DEC, bool DIRECT>
     __device__ __forceinline__ void check(const Ctx &C, const Lane &L, int &errs) { check_phase<ALGO>(C, L, wave, errs); }
-    template <bool DEC, bool WRITE>
+    template <bool DEC, bool WRITE, bool DIRECT>
     __device__ __forceinline__ void var(const Ctx &C, const Lane &L, int &errs) {
         var_phase(C, L, wave, WRITE, errs);
     }

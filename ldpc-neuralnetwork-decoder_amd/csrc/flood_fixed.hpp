@@ -206,12 +206,72 @@ __device__ __forceinline__ float direct_row(const float (&v)[CAP], const float (
     }
 }
 
+// Where a lane's decisions go in a phase that stores them directly (DIRECT: the last iteration
+// without early stop and of ES_P2), formed once at the head of the phase: the group's first output
+// element as a uniform pointer (an SGPR pair) and the lane's byte offsets from it, so that a column
+// decision is compare, select and a store at an immediate offset (COL * Z elements), and the
+// decision of a degree-1 variable met through a shift adds its rotated position to the frame's row.
+// OUT: LDPC_OUT_U8 / LDPC_OUT_F32, chosen by one uniform branch around the phase (FixedBody::check,
+// var), or kOutAny: the type is looked up at every store (the exact check update's phases, which
+// never run on real data and are not worth a copy per type).  Lanes without a frame store nothing;
+// their error count is never summed (reduce_counters).
+constexpr int kOutAny = 2;
+template <class G, int OUT>
+struct DecOut {
+    static_assert(OUT == LDPC_OUT_U8 || OUT == LDPC_OUT_F32 || OUT == kOutAny, "one form per output type");
+    // a frame's row starts at a multiple of a block, so a position inside a block can be or-ed in
+    static_assert(G::N % G::Z == 0 && (G::Z & (G::Z - 1)) == 0, "rotated(): row | position");
+    char *base;    // uniform: variable 0 of the group's first frame
+    uint32_t row;  // byte offset of the lane's frame row from base
+    uint32_t own;  // row + the lane's position k in a block
+    uint32_t kb;   // size() * k
+    uint32_t any;  // kOutAny: the element size
+    bool valid;
+    __device__ __forceinline__ uint32_t size() const {
+        if constexpr (OUT == kOutAny)
+            return any;
+        else
+            return OUT == LDPC_OUT_F32 ? 4u : 1u;
+    }
+    __device__ __forceinline__ DecOut(const Ctx &C, const Lane &L) {
+        any = C.out_dtype == LDPC_OUT_F32 ? 4u : 1u;
+        base = static_cast<char *>(C.bits) + (int64_t)L.group * (64 / G::Z) * G::N * size();
+        row = (uint32_t)L.f * (G::N * size());
+        kb = (uint32_t)L.k * size();
+        own = row + kb;
+        valid = L.valid;
+    }
+    __device__ __forceinline__ void put(uint32_t off, int bit, int &errs) const {
+        if (valid) {
+            if (size() == 4u)
+                *reinterpret_cast<float *>(base + off) = (float)bit;
+            else
+                *reinterpret_cast<uint8_t *>(base + off) = (uint8_t)bit;
+        }
+        errs += bit;
+    }
+    // variable (COL, k)
+    template <int COL>
+    __device__ __forceinline__ void col(int bit, int &errs) const { put(own + COL * G::Z * size(), bit, errs); }
+    // variable (COL, (k + S) mod Z), decided on the lane of check row k
+    template <int COL, int S>
+    __device__ __forceinline__ void rotated(int bit, int &errs) const {
+        put((row | ((kb + S * size()) & (G::Z * size() - 1))) + COL * G::Z * size(), bit, errs);
+    }
+};
+struct NoOut {  // decisions are not stored directly in this phase
+    __device__ __forceinline__ NoOut(const Ctx &, const Lane &) {}
+};
+template <class G, int OUT>
+using DecOutFor = std::conditional_t<OUT < 0, NoOut, DecOut<G, OUT>>;
+
 // BAIL: the min-sum instance holds the fast check update only and leaves the decode when the sticky
 // flag is up (flood_drive, Body::kBail); otherwise check() branches to the exact form in the kernel.
 template <class G, int ALGO, int WV, bool BAIL, int CAP, bool REG>
 struct FixedBody {
     static_assert(!BAIL || ALGO == LDPC_ALGO_MINSUM, "only min-sum has a fast and an exact check update");
     static constexpr bool kBail = BAIL;
+    static constexpr bool kPeel = true;  // decisions of the last iteration only are straight code behind the loop
     using P = FxPlan<G, WV, CAP, REG>;
     static constexpr int ZM4 = 4 * G::Z - 1;
     static constexpr int NEXT = P::T.next > 0 ? P::T.next : 1;
@@ -281,8 +341,8 @@ struct FixedBody {
         });
     }
 
-    template <int I, bool DEC, bool SLOW = false>
-    __device__ __forceinline__ void row(const Ctx &C, const Lane &L, const float (&v)[MAXDC], int &errs, float ninf, float pinf, uint32_t sgn, float alv) {
+    template <int I, bool DEC, bool SLOW, int OUT>
+    __device__ __forceinline__ void row(const Ctx &C, const Lane &L, const DecOutFor<G, OUT> &D, const float (&v)[MAXDC], int &errs, float ninf, float pinf, uint32_t sgn, float alv) {
         constexpr int R = P::chk_row(I), P0 = G::ROW_PTR[R], DC = G::ROW_PTR[R + 1] - P0;
         // an output is needed for a slot edge always, for a degree-1 edge only to take its decision
         auto needed = [](int e) constexpr { return DEC || G::ROW_SLOT[P0 + e] >= 0; };
@@ -293,8 +353,11 @@ struct FixedBody {
             } else if constexpr (SL >= 0) {
                 lds_wr_tid<SL * 256>(o);  // ds_write_addtid_b32: the slot entry of a row is slot[lane]
             } else if constexpr (DEC) {
-                if (C.direct_bits || C.ballots)  // degree-1 variable: APP = llr + c2v
-                    ext_decision(C, L, G::ROW_COL[P0 + E], 4 * P::row_shift(P0 + E), v[E] + o, errs);
+                // degree-1 variable: APP = llr + c2v; NaN < 0 is false -> 0 (traditional_decoders.py:252)
+                constexpr int COL = G::ROW_COL[P0 + E], S = P::row_shift(P0 + E);
+                const int bit = v[E] + o < 0.0f;
+                if constexpr (OUT >= 0) D.template rotated<COL, S>(bit, errs);
+                if (C.ballots) ext_ballot(C, L, COL, 4 * S, bit);
             }
         };
         if constexpr (ALGO == LDPC_ALGO_MINSUM && !SLOW && DC >= 2 && DC <= kDirectDc) {
@@ -376,21 +439,28 @@ struct FixedBody {
         }
     }
 
-    template <bool DEC>
+    // DIRECT: decisions are stored directly, in the output type picked here for the whole phase
+    template <bool DEC, bool DIRECT>
     __device__ __forceinline__ void check(const Ctx &C, const Lane &L, int &errs) {
-        if constexpr (ALGO == LDPC_ALGO_MINSUM && !BAIL) {
-            if (__builtin_amdgcn_readfirstlane(*C.flag) != 0)
-                rows<DEC, true>(C, L, errs);
-            else
-                rows<DEC, false>(C, L, errs);
-            return;
+        static_assert(DEC || !DIRECT, "stores need decisions");
+        if constexpr (ALGO == LDPC_ALGO_MINSUM && !BAIL) {  // BAIL: flood_drive has tested the flag
+            if (__builtin_amdgcn_readfirstlane(*C.flag) != 0) {
+                rows<DEC, true, (DIRECT ? kOutAny : -1)>(C, L, errs);
+                return;
+            }
         }
-        rows<DEC, false>(C, L, errs);  // BAIL: flood_drive has tested the flag
+        if constexpr (!DIRECT)
+            rows<DEC, false, -1>(C, L, errs);
+        else if (C.out_dtype == LDPC_OUT_F32)
+            rows<DEC, false, LDPC_OUT_F32>(C, L, errs);
+        else
+            rows<DEC, false, LDPC_OUT_U8>(C, L, errs);
     }
 
-    template <bool DEC, bool SLOW>
+    template <bool DEC, bool SLOW, int OUT>
     __device__ __forceinline__ void rows(const Ctx &C, const Lane &L, int &errs) {
         float va[MAXDC], vb[MAXDC];
+        const DecOutFor<G, OUT> D(C, L);
         addtid_begin(C.lds);
         const float ninf = opaque_sf(-INFINITY), pinf = opaque_sf(INFINITY);
         const uint32_t sgn = opaque_vu(0x80000000u);
@@ -400,10 +470,10 @@ struct FixedBody {
             constexpr int I = decltype(i)::value;
             if constexpr (I % 2 == 0) {
                 if constexpr (I + 1 < P::NR) load_row<I + 1>(C, L, vb);
-                row<I, DEC, SLOW>(C, L, va, errs, ninf, pinf, sgn, alv);
+                row<I, DEC, SLOW, OUT>(C, L, D, va, errs, ninf, pinf, sgn, alv);
             } else {
                 if constexpr (I + 1 < P::NR) load_row<I + 1>(C, L, va);
-                row<I, DEC, SLOW>(C, L, vb, errs, ninf, pinf, sgn, alv);
+                row<I, DEC, SLOW, OUT>(C, L, D, vb, errs, ninf, pinf, sgn, alv);
             }
         });
         addtid_end();
@@ -464,8 +534,8 @@ struct FixedBody {
         });
     }
 
-    template <int TK, bool DEC, bool WRITE>
-    __device__ __forceinline__ void task(const Ctx &C, const Lane &L, const TaskIn &in, int &errs, bool &bad) {
+    template <int TK, bool DEC, bool WRITE, int OUT>
+    __device__ __forceinline__ void task(const Ctx &C, const Lane &L, const DecOutFor<G, OUT> &D, const TaskIn &in, int &errs, bool &bad) {
         using K = Task<TK>;
         constexpr int DA = K::DA, DB = K::DB;
         f32x2 P2;
@@ -514,22 +584,35 @@ struct FixedBody {
         // summand of the APP; +-inf is absorbing), so this flag bounds the fast check path.  A zero
         // v2c needs no flag: the fast forms give the reference's values up to the sign of a zero
         // (DESIGN.md 3.1 "Exactness of the fast path", tests/test_minsum_zeros_host.py)
+        auto decide = [&](auto col, float app) {
+            constexpr int COL = decltype(col)::value;
+            const int bit = app < 0.0f;  // NaN < 0 is false -> 0 (traditional_decoders.py:252)
+            if constexpr (OUT >= 0) D.template col<COL>(bit, errs);
+            if (C.ballots) var_ballot(C, L, COL, bit);
+        };
         if constexpr (ALGO == LDPC_ALGO_MINSUM) bad |= !(fabsf(PA) < INFINITY);
-        if constexpr (DEC) {
-            if (C.direct_bits || C.ballots) var_decision(C, L, K::CA, PA, errs);
-        }
+        if constexpr (DEC) decide(ic<K::CA>{}, PA);
         if constexpr (DB > 0) {
             if constexpr (ALGO == LDPC_ALGO_MINSUM) bad |= !(fabsf(P2.y) < INFINITY);
-            if constexpr (DEC) {
-                if (C.direct_bits || C.ballots) var_decision(C, L, K::CB, P2.y, errs);
-            }
+            if constexpr (DEC) decide(ic<K::CB>{}, P2.y);
         }
     }
 
-    template <bool DEC, bool WRITE>
+    template <bool DEC, bool WRITE, bool DIRECT>
     __device__ __forceinline__ void var(const Ctx &C, const Lane &L, int &errs) {
+        static_assert(DEC || !DIRECT, "stores need decisions");
+        if constexpr (!DIRECT)
+            var_as<DEC, WRITE, -1>(C, L, errs);
+        else if (C.out_dtype == LDPC_OUT_F32)
+            var_as<DEC, WRITE, LDPC_OUT_F32>(C, L, errs);
+        else
+            var_as<DEC, WRITE, LDPC_OUT_U8>(C, L, errs);
+    }
+    template <bool DEC, bool WRITE, int OUT>
+    __device__ __forceinline__ void var_as(const Ctx &C, const Lane &L, int &errs) {
         bool bad = false;
         if constexpr (P::NT > 0) {
+            const DecOutFor<G, OUT> D(C, L);
             // software pipelining: the next task's reads are issued before the current task's adds
             // when the two hold at most kVarPipe messages together (slots are disjoint between
             // tasks, so the reads never depend on the writes in flight).  A task's own reads are
@@ -544,11 +627,11 @@ struct FixedBody {
                 constexpr bool ahead = more && Task<I>::NMSG + Task<(more ? I + 1 : I)>::NMSG <= kVarPipe;
                 if constexpr (I % 2 == 0) {
                     if constexpr (ahead) load_task<I + 1>(C, tb);
-                    task<I, DEC, WRITE>(C, L, ta, errs, bad);
+                    task<I, DEC, WRITE, OUT>(C, L, D, ta, errs, bad);
                     if constexpr (more && !ahead) load_task<(more ? I + 1 : I)>(C, tb);
                 } else {
                     if constexpr (ahead) load_task<I + 1>(C, ta);
-                    task<I, DEC, WRITE>(C, L, tb, errs, bad);
+                    task<I, DEC, WRITE, OUT>(C, L, D, tb, errs, bad);
                     if constexpr (more && !ahead) load_task<(more ? I + 1 : I)>(C, ta);
                 }
             });
