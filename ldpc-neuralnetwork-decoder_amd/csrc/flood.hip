@@ -26,8 +26,11 @@
 // Translation units: flood_dev.hpp (device code shared by all), flood_fixed_ms.hip / flood_fixed_bp.hip
 // (compile-time schedules: flood_fixed.hpp), flood_stream.hip (streaming decoders), flood_layered.hip
 // (layered min-sum), flood_layered_stream.hip (layered min-sum on the streaming layout), flood_half.hip
-// (half-precision min-sum, two frames per lane), and this file
-// (table-driven kernel, early-stop passes, host dispatch, the C ABI).
+// (half-precision min-sum, two frames per lane), flood_layered_stream_half.hip (half-precision layered
+// min-sum on streaming kernels of its own), and this file (table-driven kernel, early-stop passes, host
+// dispatch, the C ABI).  Shared by several: flood_stream.hpp (the streaming layout's argument block, min-sum
+// row rule, workspace carve and layered host loop), half_pair.hpp (the packed-binary16 pair vocabulary of the
+// two half-precision files), flood_host.hpp (their host interfaces), common.hpp (errors, the workspace Arena).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +38,7 @@
 #include <vector>
 
 #include "flood_host.hpp"
+#include "half_pair.hpp"
 
 namespace ldpc {
 
@@ -206,23 +210,21 @@ struct FloodWs {
 FloodWs flood_ws(const ldpc_graph *g, int64_t B, int max_iter, int early_stop, void *base) {
     FloodWs w{};
     const int64_t nwg = (B + g->FG - 1) / g->FG;
-    char *p = static_cast<char *>(base);
-    size_t off = 0;
-    auto take = [&](size_t n) { char *q = p ? p + off : nullptr; off += align256(n); return q; };
-    w.partials = reinterpret_cast<uint32_t *>(take((size_t)nwg * kPartRow * 4));
-    w.redo = reinterpret_cast<uint32_t *>(take((size_t)(nwg + 1) * 4));
+    Arena a(base);
+    w.partials = a.take<uint32_t>(nwg * kPartRow * 4);
+    w.redo = a.take<uint32_t>((nwg + 1) * 4);
     if (early_stop == LDPC_ES_BATCH) {
         EsWs &e = w.es;
         e.nvw = (max_iter + 31) / 32;
-        e.words = reinterpret_cast<uint64_t *>(take((size_t)nwg * max_iter * g->Nb * 8));
-        e.valid = reinterpret_cast<uint32_t *>(take((size_t)B * e.nvw * 4));
-        w.all = reinterpret_cast<uint32_t *>(take(64 * 4));
-        e.cand = reinterpret_cast<uint64_t *>(take((size_t)nwg * g->Nb * 8));
-        e.twg = reinterpret_cast<int32_t *>(take((size_t)nwg * 4));
-        e.ctl = reinterpret_cast<int32_t *>(take(64));
-        e.staged = reinterpret_cast<uint64_t *>(take(64));
+        e.words = a.take<uint64_t>(nwg * max_iter * g->Nb * 8);
+        e.valid = a.take<uint32_t>(B * e.nvw * 4);
+        w.all = a.take<uint32_t>(64 * 4);
+        e.cand = a.take<uint64_t>(nwg * g->Nb * 8);
+        e.twg = a.take<int32_t>(nwg * 4);
+        e.ctl = a.take<int32_t>(64);
+        e.staged = a.take<uint64_t>(64);
     }
-    w.bytes = (int64_t)off;
+    w.bytes = a.bytes;
     return w;
 }
 
@@ -275,6 +277,18 @@ int reduce_rows(const ldpc_graph *g, int64_t B, const uint32_t *partials, uint64
     const int fg = frames_per_wg > 0 ? frames_per_wg : g->FG;
     const int64_t nwg = (B + fg - 1) / fg;
     return reduce_counter_rows(partials, nwg, counters, batch_iters, gate, s);
+}
+
+// the refusals of ldpc_flood_decode that differ only in the decoder's name
+int no_batch_stop(const char *name, const char *why = "") {
+    return fail(LDPC_EINVAL, std::string(name) + " has no batch-global stop" + why + ": use LDPC_ES_OFF or LDPC_ES_FRAME");
+}
+
+int needs_lds_schedule(const char *name, const ldpc_graph *g) {
+    return fail(LDPC_EUNSUPPORTED,
+                std::string(name) + " needs the LDS-resident schedule, and this graph decodes on the streaming "
+                "kernels (lifting Z = " + std::to_string(g->Z) + (g->lds_ok ? "" : ", schedule encoding does not fit") +
+                ", or LDPC_FLOOD_STREAM is set)");
 }
 
 template <int ALGO>
@@ -382,14 +396,11 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
     if (out_dtype != LDPC_OUT_U8 && out_dtype != LDPC_OUT_F32) return fail(LDPC_EINVAL, "unknown out_dtype");
     if (B < 0) return fail(LDPC_EINVAL, "negative batch");
     if (max_iter < 1 || max_iter > 1024) return fail(LDPC_EINVAL, "max_iter must be in [1, 1024]");
-    if (layered && early_stop == LDPC_ES_BATCH)
-        return fail(LDPC_EINVAL, "layered min-sum has no batch-global stop (LDPC_ES_BATCH mirrors the reference's "
-                                 "flooding classes): use LDPC_ES_OFF or LDPC_ES_FRAME");
-    if (half && early_stop == LDPC_ES_BATCH)
-        return fail(LDPC_EINVAL, "half-precision min-sum has no batch-global stop: use LDPC_ES_OFF or LDPC_ES_FRAME");
-    if (layered_half && early_stop == LDPC_ES_BATCH)
-        return fail(LDPC_EINVAL, "half-precision layered min-sum has no batch-global stop: use LDPC_ES_OFF or "
-                                 "LDPC_ES_FRAME");
+    if (early_stop == LDPC_ES_BATCH) {
+        if (layered) return no_batch_stop("layered min-sum", " (LDPC_ES_BATCH mirrors the reference's flooding classes)");
+        if (half) return no_batch_stop("half-precision min-sum");
+        if (layered_half) return no_batch_stop("half-precision layered min-sum");
+    }
     if (half || layered_half) {
         const uint32_t a = half_alpha_bits(alpha);  // 0 <= half(alpha) <= 1 (a NaN fails both)
         if (!(a <= 0x3c00u || a == 0x8000u))
@@ -420,11 +431,7 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
     const bool layered_stream = algo == LDPC_ALGO_LAYERED_MINSUM_ANY && streaming;
     if (layered && !layered_stream) {
         // LDS-resident only
-        if (streaming)
-            return fail(LDPC_EUNSUPPORTED,
-                        "layered min-sum needs the LDS-resident schedule, and this graph decodes on the streaming "
-                        "kernels (lifting Z = " + std::to_string(g->Z) + (g->lds_ok ? "" : ", schedule encoding does not fit") +
-                        ", or LDPC_FLOOD_STREAM is set)");
+        if (streaming) return needs_lds_schedule("layered min-sum", g);
         if (!g->lt.prog || layered_lds_bytes(g, early_stop) > kLdsMax)
             return fail(LDPC_EUNSUPPORTED, "layered min-sum: posteriors and messages of one wave's frames need " +
                                                std::to_string(layered_lds_bytes(g, early_stop)) + " bytes of LDS, above " +
@@ -432,11 +439,7 @@ extern "C" int ldpc_flood_decode(const ldpc_graph *g, int algo, const float *d_l
     }
     if (half) {
         // LDS-resident only; no partial sum may overflow binary16: 33 * 1024 < 65504
-        if (streaming)
-            return fail(LDPC_EUNSUPPORTED,
-                        "half-precision min-sum needs the LDS-resident schedule, and this graph decodes on the streaming "
-                        "kernels (lifting Z = " + std::to_string(g->Z) + (g->lds_ok ? "" : ", schedule encoding does not fit") +
-                        ", or LDPC_FLOOD_STREAM is set)");
+        if (streaming) return needs_lds_schedule("half-precision min-sum", g);
         if (g->max_dv > 32)
             return fail(LDPC_EUNSUPPORTED, "half-precision min-sum: variable degree " + std::to_string(g->max_dv) + " above 32");
         if (half_lds_bytes(g) > kLdsMax)

@@ -38,20 +38,11 @@
 #include <string>
 
 #include "flood_host.hpp"
+#include "half_pair.hpp"
 
 namespace ldpc {
 
 namespace {
-
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ h2 as_h(uint32_t u) { return __builtin_bit_cast(h2, u); }
-__device__ __forceinline__ uint32_t as_u(h2 h) { return __builtin_bit_cast(uint32_t, h); }
-// IEEE minimum / maximum: one v_pk_minimum3_f16 / v_pk_maximum3_f16, no canonicalising v_pk_max
-__device__ __forceinline__ h2 hmin(h2 a, h2 b) { return __builtin_elementwise_minimum(a, b); }
-__device__ __forceinline__ h2 hmax(h2 a, h2 b) { return __builtin_elementwise_maximum(a, b); }
-
-constexpr uint32_t kSign2 = 0x80008000u, kAbs2 = 0x7fff7fffu, kInf2 = 0x7c007c00u;
-constexpr uint32_t kClampPos2 = 0x64006400u, kClampNeg2 = 0xe400e400u;  // +-1024
 
 struct HLane {
     int lane;        // 0..63 = f * Z + k
@@ -70,8 +61,7 @@ struct HCtx {
     FloodTables T;
     char *lds;
     uint64_t *words;   // [2][Nb + 1] decision ballots + invalid-lane word, low frames then high frames
-    // uniform constants in VGPRs (a VALU op with an SGPR source issues at half rate)
-    uint32_t a2, cpos, cneg, sign, absm;
+    HConst K;
     int out_dtype;
     void *bits;
     bool direct_bits;  // LDPC_ES_OFF, final iteration: decisions straight to HBM
@@ -81,8 +71,6 @@ struct HCtx {
 __device__ __forceinline__ uint32_t ldu(const char *lds, int off) { return *reinterpret_cast<const uint32_t *>(lds + off); }
 __device__ __forceinline__ void stu(char *lds, int off, uint32_t v) { *reinterpret_cast<uint32_t *>(lds + off) = v; }
 
-__device__ __forceinline__ h2 hclamp(const HCtx &C, h2 v) { return hmin(hmax(v, as_h(C.cneg)), as_h(C.cpos)); }
-
 // x = clamp(half(llr)) of the lane's two frames at a byte offset inside an LLR row.  A magnitude that
 // rounds to infinity clamps to +-C; a NaN stays one (its frame's outputs are unspecified).
 __device__ __forceinline__ h2 x_at(const HCtx &C, const HLane &L, int byte_off) {
@@ -91,7 +79,7 @@ __device__ __forceinline__ h2 x_at(const HCtx &C, const HLane &L, int byte_off) 
     h2 x;
     x.x = (_Float16)lo;
     x.y = (_Float16)hi;
-    return hclamp(C, x);
+    return hclamp(C.K, x);
 }
 
 // decisions of one column: bit = (app < 0) per half, to HBM and / or the ballots.  rot: the column's
@@ -117,12 +105,6 @@ __device__ __forceinline__ void decide(const HCtx &C, const HLane &L, int col, i
 }
 
 // ---------------------------------------------------------------- check node update
-// out = sign | magnitude: prod >= +0 (a >= 0, min >= 0), so its sign bits are free for the parity
-__device__ __forceinline__ uint32_t signed_c2v(const HCtx &C, uint32_t par, uint32_t v, h2 excl_min) {
-    const uint32_t prod = as_u(as_h(C.a2) * excl_min);  // rounded once
-    return ((par ^ v) & C.sign) | prod;
-}
-
 template <int DC>
 __device__ __forceinline__ void hcheck_task(const HCtx &C, const HLane &L, const int32_t *prog, int (&errs)[2]) {
     uint32_t v[DC];
@@ -133,39 +115,21 @@ __device__ __forceinline__ void hcheck_task(const HCtx &C, const HLane &L, const
         const int lo = w[e] & kLowMask, s4 = (w[e] >> kShiftBit) & 0xFF;
         v[e] = w[e] < 0 ? as_u(x_at(C, L, L.col_off(lo, s4))) : ldu(C.lds, lo + L.lane4);
     }
-    uint32_t par = v[0];
-#pragma unroll
-    for (int e = 1; e < DC; ++e) par ^= v[e];
-    // exclusive minimum of the magnitudes: prefix and suffix minima
-    h2 pre[DC], suf[DC];
-    pre[0] = as_h(v[0] & C.absm);
-#pragma unroll
-    for (int e = 1; e < DC; ++e) pre[e] = hmin(pre[e - 1], as_h(v[e] & C.absm));
-    suf[DC - 1] = as_h(v[DC - 1] & C.absm);
-#pragma unroll
-    for (int e = DC - 2; e >= 0; --e) suf[e] = hmin(suf[e + 1], as_h(v[e] & C.absm));
+    // the empty minimum is +inf here: the contract's min over no message ("Half-precision min-sum",
+    // include/ldpc_amd.h), as in the float32 rule.  The layered form's is C (half_pair.hpp).
+    uint32_t out[DC];
+    half_check_rule<DC>(C.K, v, out, as_h(kInf2));
 #pragma unroll
     for (int e = 0; e < DC; ++e) {
-        h2 m;
-        if (DC == 1)
-            m = as_h(kInf2);  // the empty minimum
-        else if (e == 0)
-            m = suf[1];
-        else if (e == DC - 1)
-            m = pre[DC - 2];
-        else
-            m = hmin(pre[e - 1], suf[e + 1]);
-        const uint32_t o = signed_c2v(C, par, v[e], m);
         const int lo = w[e] & kLowMask;
         if (w[e] >= 0)
-            stu(C.lds, lo + L.lane4, o);
+            stu(C.lds, lo + L.lane4, out[e]);
         else if (C.direct_bits || C.ballots)  // degree-1 variable: app = x + c2v
-            decide(C, L, lo, (w[e] >> kShiftBit) & 0xFF, as_h(v[e]) + as_h(o), errs);
+            decide(C, L, lo, (w[e] >> kShiftBit) & 0xFF, as_h(v[e]) + as_h(out[e]), errs);
     }
 }
 
-// Any degree: the row's two smallest magnitudes in a first pass, the exclusive minimum chosen per half in a
-// second (the excluded minimum is m2 exactly when |v| == m1: a tie at m1 puts m1 in m2 as well).
+// Any degree: the two-pass form (half_two_min_step / half_excl_select), the row read from LDS twice.
 __device__ __forceinline__ void hcheck_task_dyn(const HCtx &C, const HLane &L, const int32_t *prog, int dc,
                                                 int (&errs)[2]) {
     auto rd = [&](int e) -> uint32_t {
@@ -173,22 +137,16 @@ __device__ __forceinline__ void hcheck_task_dyn(const HCtx &C, const HLane &L, c
         const int lo = w & kLowMask;
         return w < 0 ? as_u(x_at(C, L, L.col_off(lo, (w >> kShiftBit) & 0xFF))) : ldu(C.lds, lo + L.lane4);
     };
-    h2 m1 = as_h(kInf2), m2 = as_h(kInf2);
+    h2 m1 = as_h(kInf2), m2 = as_h(kInf2);  // the empty minimum, as in hcheck_task
     uint32_t par = 0;
     for (int e = 0; e < dc; ++e) {
         const uint32_t x = rd(e);
-        const h2 a = as_h(x & C.absm);
         par ^= x;
-        m2 = hmin(m2, hmax(m1, a));
-        m1 = hmin(m1, a);
+        half_two_min_step(m1, m2, as_h(x & C.K.absm));
     }
     for (int e = 0; e < dc; ++e) {
         const uint32_t x = rd(e);
-        const h2 a = as_h(x & C.absm);
-        h2 m;
-        m.x = a.x == m1.x ? m2.x : m1.x;
-        m.y = a.y == m1.y ? m2.y : m1.y;
-        const uint32_t o = signed_c2v(C, par, x, m);
+        const uint32_t o = signed_c2v(C.K, par, x, half_excl_select(as_h(x & C.K.absm), m1, m2));
         const int32_t w = tab(prog, e);
         const int lo = w & kLowMask;
         if (w >= 0)
@@ -218,7 +176,7 @@ __device__ __forceinline__ void hvar_task(const HCtx &C, const HLane &L, const i
         }
         if (write) {
 #pragma unroll
-            for (int e = 0; e < DV; ++e) stu(C.lds, off[e], as_u(hclamp(C, acc[e])));
+            for (int e = 0; e < DV; ++e) stu(C.lds, off[e], as_u(hclamp(C.K, acc[e])));
         }
     }
     if (C.direct_bits || C.ballots) decide(C, L, col, 0, P, errs);
@@ -237,7 +195,7 @@ __device__ __forceinline__ void hvar_task_dyn(const HCtx &C, const HLane &L, con
         h2 acc = P;
         for (int q = e + 1; q < dv; ++q) acc = acc + as_h(ldu(C.lds, off(q)));
         P = P + cp;
-        if (write) stu(C.lds, o, as_u(hclamp(C, acc)));  // slot e is not read again
+        if (write) stu(C.lds, o, as_u(hclamp(C.K, acc)));  // slot e is not read again
     }
     if (C.direct_bits || C.ballots) decide(C, L, col, 0, P, errs);
 }
@@ -408,11 +366,7 @@ __global__ __launch_bounds__(256) void flood_half_kernel(FloodTables T, const fl
     C.T = T;
     C.lds = lds;
     C.words = reinterpret_cast<uint64_t *>(lds + (size_t)T.nslots * 256 + 8);
-    C.a2 = opaque_vu(alpha2);
-    C.cpos = opaque_vu(kClampPos2);
-    C.cneg = opaque_vu(kClampNeg2);
-    C.sign = opaque_vu(kSign2);
-    C.absm = opaque_vu(kAbs2);
+    C.K = make_const(alpha2);
     C.out_dtype = out_dtype;
     C.bits = bits;
     C.direct_bits = false;
@@ -486,13 +440,6 @@ __global__ __launch_bounds__(256) void flood_half_kernel(FloodTables T, const fl
 size_t half_lds_bytes(const ldpc_graph *g) {
     const size_t b = (size_t)g->nslots * 256 + 8 + 2 * (size_t)(g->Nb + 1) * sizeof(uint64_t);
     return std::max<size_t>(b, 4 * 64 * (size_t)g->ft.W * sizeof(uint32_t));  // hreduce_counters
-}
-
-uint32_t half_alpha_bits(float alpha) {
-    const _Float16 a = (_Float16)alpha;  // round-to-nearest-even
-    uint16_t u;
-    __builtin_memcpy(&u, &a, sizeof u);
-    return u;
 }
 
 template <int ES>

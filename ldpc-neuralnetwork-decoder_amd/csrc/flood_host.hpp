@@ -8,7 +8,6 @@
 namespace ldpc {
 
 constexpr int kStreamMaxDeg = 32;  // register windows of stream_check_kernel / stream_var_kernel
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 // flood.hip: fold per-workgroup counter rows (counters_reduce_kernel)
 int reduce_counter_rows(const uint32_t *partials, int64_t nwg, uint64_t *counters, int32_t *batch_iters,
@@ -53,9 +52,8 @@ int run_layered_stream(const FloodCall &c);
 
 // flood_half.hip: half-precision min-sum (LDPC_ALGO_MINSUM_F16; LDS-resident only, c.es is LDPC_ES_OFF or
 // LDPC_ES_FRAME, c.alpha already checked).  c.work holds the counter rows, one per 2 * FG frames: the head
-// of the flooding workspace of the same arguments.  half_alpha_bits: binary16 bits of half(alpha).
+// of the flooding workspace of the same arguments.  (half_alpha_bits, which checks c.alpha: half_pair.hpp.)
 size_t half_lds_bytes(const ldpc_graph *g);
-uint32_t half_alpha_bits(float alpha);
 int run_half(const FloodCall &c);
 
 // flood_layered_stream_half.hip: half-precision layered min-sum (LDPC_ALGO_LAYERED_MINSUM_F16) on streaming

@@ -41,20 +41,12 @@
 #include <string>
 
 #include "flood_stream.hpp"
+#include "half_pair.hpp"
 
 namespace ldpc {
 
 namespace {
 
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ h2 as_h(uint32_t u) { return __builtin_bit_cast(h2, u); }
-__device__ __forceinline__ uint32_t as_u(h2 h) { return __builtin_bit_cast(uint32_t, h); }
-// IEEE minimum / maximum: one v_pk_minimum3_f16 / v_pk_maximum3_f16, no canonicalising v_pk_max
-__device__ __forceinline__ h2 hmin(h2 a, h2 b) { return __builtin_elementwise_minimum(a, b); }
-__device__ __forceinline__ h2 hmax(h2 a, h2 b) { return __builtin_elementwise_maximum(a, b); }
-
-constexpr uint32_t kSign2 = 0x80008000u, kAbs2 = 0x7fff7fffu;
-constexpr uint32_t kClampPos2 = 0x64006400u, kClampNeg2 = 0xe400e400u;  // +-1024
 constexpr int kPairFrames = 128;  // frames of a wave: the row stride is a multiple of it
 
 struct HalfArgs {
@@ -70,15 +62,6 @@ struct HalfArgs {
     int es;
 };
 
-// uniform constants in VGPRs (a VALU op with an SGPR source issues at half rate)
-struct HConst {
-    uint32_t a2, cpos, cneg, sign, absm;
-};
-__device__ __forceinline__ HConst make_const(uint32_t a2) {
-    return HConst{opaque_vu(a2), opaque_vu(kClampPos2), opaque_vu(kClampNeg2), opaque_vu(kSign2), opaque_vu(kAbs2)};
-}
-__device__ __forceinline__ h2 hclamp(const HConst &K, h2 v) { return hmin(hmax(v, as_h(K.cneg)), as_h(K.cpos)); }
-
 // which of the pair's two frames exist and still run; false: the thread has nothing to do
 __device__ __forceinline__ bool pair_live(const HalfArgs &S, int64_t p, bool (&live)[2]) {
 #pragma unroll
@@ -88,64 +71,6 @@ __device__ __forceinline__ bool pair_live(const HalfArgs &S, int64_t p, bool (&l
         if (live[h] && S.es == LDPC_ES_FRAME) live[h] = S.done[b] == 0;
     }
     return live[0] || live[1];
-}
-
-// out = sign | magnitude: prod >= +0 (a >= 0, min >= 0), so its sign bits are free for the parity
-__device__ __forceinline__ uint32_t signed_c2v(const HConst &K, uint32_t par, uint32_t v, h2 excl_min) {
-    const uint32_t prod = as_u(as_h(K.a2) * excl_min);  // rounded once
-    return ((par ^ v) & K.sign) | prod;
-}
-
-// The check rule on a row of packed halves held in registers.  The minimum starts at C: every |t| <= C, so
-// that changes nothing for DC >= 2 and makes a degree-1 check send +a * C.  sgn(0) = 0 needs no code: if
-// another message of the row is zero the exclusive minimum is 0 and the result is a zero whatever its sign,
-// and if only t_k itself is zero its sign bit cancels in the XOR.
-template <int DC>
-__device__ __forceinline__ void hcheck_rule(const HConst &K, const uint32_t (&v)[DC], uint32_t (&out)[DC]) {
-    uint32_t par = v[0];
-#pragma unroll
-    for (int e = 1; e < DC; ++e) par ^= v[e];
-    if constexpr (DC == 1) {
-        out[0] = signed_c2v(K, par, v[0], as_h(K.cpos));  // the empty minimum
-    } else if constexpr (DC <= 12) {
-        // exclusive minimum of the magnitudes: prefix and suffix minima
-        h2 pre[DC], suf[DC];
-        pre[0] = as_h(v[0] & K.absm);
-#pragma unroll
-        for (int e = 1; e < DC; ++e) pre[e] = hmin(pre[e - 1], as_h(v[e] & K.absm));
-        suf[DC - 1] = as_h(v[DC - 1] & K.absm);
-#pragma unroll
-        for (int e = DC - 2; e >= 0; --e) suf[e] = hmin(suf[e + 1], as_h(v[e] & K.absm));
-#pragma unroll
-        for (int e = 0; e < DC; ++e) {
-            h2 m;
-            if (e == 0)
-                m = suf[1];
-            else if (e == DC - 1)
-                m = pre[DC - 2];
-            else
-                m = hmin(pre[e - 1], suf[e + 1]);
-            out[e] = signed_c2v(K, par, v[e], m);
-        }
-    } else {
-        // the row's two smallest magnitudes in a first pass, the exclusive minimum chosen per half in a second
-        // (the excluded minimum is m2 exactly when |v| == m1: a tie at m1 puts m1 in m2 as well)
-        h2 m1 = as_h(K.cpos), m2 = as_h(K.cpos);
-#pragma unroll
-        for (int e = 0; e < DC; ++e) {
-            const h2 a = as_h(v[e] & K.absm);
-            m2 = hmin(m2, hmax(m1, a));
-            m1 = hmin(m1, a);
-        }
-#pragma unroll
-        for (int e = 0; e < DC; ++e) {
-            const h2 a = as_h(v[e] & K.absm);
-            h2 m;
-            m.x = a.x == m1.x ? m2.x : m1.x;
-            m.y = a.y == m1.y ? m2.y : m1.y;
-            out[e] = signed_c2v(K, par, v[e], m);
-        }
-    }
 }
 
 }  // namespace
@@ -207,8 +132,10 @@ __global__ __launch_bounds__(256) void layered_half_kernel(HalfArgs S, const int
         else
             t[e] = as_u(hclamp(K, as_h(t[e]) - as_h(xv[e] < 0 ? m[e] : 0u)));
     }
+    // the minimum starts at C, not at +inf ("Half-precision layered min-sum", include/ldpc_amd.h): every |t| <= C,
+    // so a degree-1 check sends +a * C and nothing is ever infinite.  The flooding form's is +inf (half_pair.hpp).
     uint32_t c[DC];
-    hcheck_rule<DC>(K, t, c);
+    half_check_rule<DC>(K, t, c, as_h(K.cpos));
 #pragma unroll
     for (int e = 0; e < DC; ++e) {
         const h2 app = as_h(t[e]) + as_h(c[e]);
@@ -252,35 +179,27 @@ HalfWs half_ws(const ldpc_graph *g, int64_t B, void *base) {
     HalfWs w{};
     const int64_t Bs = (B + kPairFrames - 1) / kPairFrames * kPairFrames;
     w.Bw = Bs / 2;
-    char *p = static_cast<char *>(base);
-    size_t off = 0;
-    auto take = [&](size_t n) { char *q = p ? p + off : nullptr; off += align256(n); return q; };
-    w.msgW = reinterpret_cast<uint32_t *>(take((size_t)g->E * Bs * 2));
-    w.appW = reinterpret_cast<uint32_t *>(take((size_t)g->N * Bs * 2));
-    w.bitsT = reinterpret_cast<uint8_t *>(take((size_t)g->N * B));
-    w.done = reinterpret_cast<uint8_t *>(take((size_t)B));
-    w.iters = reinterpret_cast<int32_t *>(take((size_t)B * 4));
-    w.partials = reinterpret_cast<uint32_t *>(take((size_t)((B + 63) / 64) * kPartRow * 4));
-    w.bytes = (int64_t)off;
+    Arena a(base);
+    w.msgW = a.take<uint32_t>(g->E * Bs * 2);
+    w.appW = a.take<uint32_t>(g->N * Bs * 2);
+    w.bitsT = a.take<uint8_t>(g->N * B);
+    w.done = a.take<uint8_t>(B);
+    w.iters = a.take<int32_t>(B * 4);
+    w.partials = a.take<uint32_t>((B + 63) / 64 * kPartRow * 4);
+    w.bytes = a.bytes;
     return w;
 }
 
 template <bool FIRST>
 void launch_layers(const ldpc_graph *g, const HalfArgs &S, hipStream_t s) {
-    const unsigned gx = (unsigned)(((S.B + 1) / 2 + 255) / 256);
-    for (size_t q = 0; q + 3 < g->lay_seg.size(); q += 4) {  // {run, degree, offset, count}: runs ascending
-        const int d = g->lay_seg[q + 1], n = g->lay_seg[q + 3];
-        for (int k0 = 0; k0 < n; k0 += kGridY) {
-            const dim3 grid(gx, (unsigned)std::min(kGridY, n - k0));
-            const int32_t *rows = g->lay_order + g->lay_seg[q + 2] + k0;
-            switch (d) {  // degree 0: nothing to update; degrees above 32 are refused on the host
+    per_segment(g, (unsigned)(((S.B + 1) / 2 + 255) / 256), [&](int d, dim3 grid, const int32_t *rows) {
+        switch (d) {  // degree 0: nothing to update; degrees above 32 are refused on the host
 #define X(k) case k: hipLaunchKernelGGL((layered_half_kernel<k, FIRST>), grid, dim3(256), 0, s, S, rows); break;
-                LDPC_STREAM_DEG_CASES(X)
+            LDPC_STREAM_DEG_CASES(X)
 #undef X
-                default: break;
-            }
+            default: break;
         }
-    }
+    });
 }
 
 }  // namespace
@@ -290,43 +209,29 @@ int64_t layered_half_ws_bytes(const ldpc_graph *g, int64_t B) { return half_ws(g
 int run_layered_stream_half(const FloodCall &c) {
     const ldpc_graph *g = c.g;
     const int64_t B = c.B;
-    const int max_iter = c.max_iter, es = c.es;
     hipStream_t s = c.s;
     const HalfWs w = half_ws(g, B, c.work);
     const uint32_t a = half_alpha_bits(c.alpha);
     const HalfArgs S{g->chk_ptr, g->ev, g->var_ptr, g->ext_var, g->N, B, w.Bw, w.msgW, w.appW, w.bitsT, w.done,
-                     a | (a << 16), es};
+                     a | (a << 16), c.es};
     // the float32 streaming decoders' passes read only the graph, B, bitsT, done, iters and es of this
-    StreamArgs T{};
-    T.chk_ptr = g->chk_ptr; T.ev = g->ev; T.var_ptr = g->var_ptr; T.var_edge = g->var_edge;
-    T.M = g->M; T.N = g->N; T.E = g->E; T.B = B;
-    T.bitsT = w.bitsT; T.done = w.done; T.iters = w.iters;
-    T.alpha = c.alpha; T.es = es; T.ext_var = g->ext_var;
-    LDPC_HIP(hipMemsetAsync(w.done, 0, (size_t)B, s));
-    const dim3 tgrid((unsigned)(2 * w.Bw / 64), (unsigned)((g->N + 63) / 64));
-    hipLaunchKernelGGL(layered_half_transpose_kernel, tgrid, dim3(256), 0, s, c.llr, B, g->N, w.Bw, w.appW);
-    LDPC_CHECK_LAUNCH("half layered stream transpose");
+    const StreamArgs T = make_stream_args(g, B, c.alpha, c.es, nullptr, nullptr, w.bitsT, w.done, w.iters, nullptr,
+                                          nullptr, g->ext_var);
     const unsigned gx = (unsigned)(((B + 1) / 2 + 255) / 256);
-    for (int it = 0; it < max_iter; ++it) {
-        if (it == 0)
-            launch_layers<true>(g, S, s);
-        else
-            launch_layers<false>(g, S, s);
-        if (es == LDPC_ES_FRAME || it == max_iter - 1) {
+    return layered_stream_drive(
+        c, T, w.partials, "half layered stream",
+        [&]() -> int {
+            const dim3 tgrid((unsigned)(2 * w.Bw / 64), (unsigned)((g->N + 63) / 64));
+            hipLaunchKernelGGL(layered_half_transpose_kernel, tgrid, dim3(256), 0, s, c.llr, B, g->N, w.Bw, w.appW);
+            LDPC_CHECK_LAUNCH("half layered stream transpose");
+            return LDPC_OK;
+        },
+        [&](bool first) { first ? launch_layers<true>(g, S, s) : launch_layers<false>(g, S, s); },
+        [&] {
             for (int j0 = 0; j0 < g->N; j0 += kGridY)
                 hipLaunchKernelGGL(layered_half_decide_kernel, dim3(gx, (unsigned)std::min(kGridY, g->N - j0)),
                                    dim3(256), 0, s, S, j0);
-            if (es == LDPC_ES_FRAME) launch_stream_syndrome(T, it, s);
-        }
-        LDPC_CHECK_LAUNCH("half layered stream iteration");
-    }
-    const bool want = c.counters || c.batch_iters;
-    launch_stream_emit(T, max_iter, c.out_dtype, c.bits, c.iters, want ? w.partials : nullptr, s);
-    LDPC_CHECK_LAUNCH("half layered stream emit");
-    if (!want) return LDPC_OK;
-    // batch_iters: ES off was set before the launch; otherwise the largest per-frame count
-    return reduce_counter_rows(w.partials, (B + 63) / 64, c.counters, es == LDPC_ES_OFF ? nullptr : c.batch_iters,
-                               nullptr, s);
+        });
 }
 
 }  // namespace ldpc

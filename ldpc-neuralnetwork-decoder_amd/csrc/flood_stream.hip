@@ -17,7 +17,8 @@ namespace ldpc {
 // operation sequences are the LDS kernels' (= the reference's), so results are bit-identical
 // (min-sum) / identical (BP) across the two paths.  Early stop keeps the reference's rules with
 // device flags: a finished batch (LDPC_ES_BATCH) or frame (LDPC_ES_FRAME) skips the later launches.
-// StreamArgs, the workspace carve and the passes that flood_layered_stream.hip runs too: flood_stream.hpp.
+// StreamArgs, the min-sum row rule, the workspace carve and the passes that the layered streaming decoders
+// run too: flood_stream.hpp.
 // (B, N) -> (N, B) through 64 x 64 LDS tiles
 __global__ __launch_bounds__(256) void stream_transpose_llr_kernel(const float *__restrict__ llr, int64_t B, int N,
                                                                    float *__restrict__ llrT) {
@@ -49,29 +50,7 @@ __device__ __forceinline__ void stream_row(const StreamArgs &S, float *m, int e0
     }
     float out[DC];
     if constexpr (ALGO == LDPC_ALGO_MINSUM) {
-        // the LDS kernels' fast path (two minima by v_min / v_med3, sign parity by xor) when the
-        // row has no zero and no NaN message; else MinSumStats (exact torch.sign semantics)
-        const float ninf = opaque_sf(-INFINITY);
-        float m1 = fabsf(v[0]), m2 = opaque_sf(INFINITY);
-        bool special = is_zero_sign(v[0]);
-#pragma unroll
-        for (int e = 1; e < DC; ++e) {
-            two_min_step(m1, m2, v[e], ninf);
-            special |= is_zero_sign(v[e]);
-        }
-        if (!special) {
-            const uint32_t par = sign_parity_n<DC>(v) & 0x80000000u;
-            const uint32_t s1 = __float_as_uint(S.alpha * m1) ^ par, s2 = __float_as_uint(S.alpha * m2) ^ par;
-#pragma unroll
-            for (int e = 0; e < DC; ++e)
-                out[e] = __uint_as_float((__float_as_uint(v[e]) & 0x80000000u) ^ (fabsf(v[e]) == m1 ? s2 : s1));
-        } else {
-            MinSumStats st;
-#pragma unroll
-            for (int e = 0; e < DC; ++e) st.add(e, v[e]);
-#pragma unroll
-            for (int e = 0; e < DC; ++e) out[e] = st.c2v(e, v[e], S.alpha);
-        }
+        minsum_rule<DC>(v, S.alpha, out);
     } else {
         // c2v_e = 2 atanh(prod_{f != e} tanh(v_f / 2)), product from 1.0 ascending (:72-81):
         // acc[e] = P_e * t_{e+1} * ... built column by column, as the LDS kernels do
@@ -313,18 +292,16 @@ __global__ __launch_bounds__(256) void custom_output_kernel(StreamArgs S, float 
 
 StreamWs stream_ws(const ldpc_graph *g, int64_t B, int max_iter, void *base) {
     StreamWs w{};
-    char *p = static_cast<char *>(base);
-    size_t off = 0;
-    auto take = [&](size_t n) { char *q = p ? p + off : nullptr; off += align256(n); return q; };
-    w.msg = reinterpret_cast<float *>(take((size_t)g->E * B * 4));
-    w.llrT = reinterpret_cast<float *>(take((size_t)g->N * B * 4));
-    w.bitsT = reinterpret_cast<uint8_t *>(take((size_t)g->N * B));
-    w.done = reinterpret_cast<uint8_t *>(take((size_t)B));
-    w.iters = reinterpret_cast<int32_t *>(take((size_t)B * 4));
-    w.ctl = reinterpret_cast<int32_t *>(take(64));
-    w.invalid = reinterpret_cast<int32_t *>(take((size_t)max_iter * 4));
-    w.partials = reinterpret_cast<uint32_t *>(take((size_t)((B + 63) / 64) * kPartRow * 4));
-    w.bytes = (int64_t)off;
+    Arena a(base);
+    w.msg = a.take<float>(g->E * B * 4);
+    w.llrT = a.take<float>(g->N * B * 4);
+    w.bitsT = a.take<uint8_t>(g->N * B);
+    w.done = a.take<uint8_t>(B);
+    w.iters = a.take<int32_t>(B * 4);
+    w.ctl = a.take<int32_t>(64);
+    w.invalid = a.take<int32_t>((int64_t)max_iter * 4);
+    w.partials = a.take<uint32_t>((B + 63) / 64 * kPartRow * 4);
+    w.bytes = a.bytes;
     return w;
 }
 
@@ -383,14 +360,12 @@ int run_stream(const FloodCall &c) {
     const int max_iter = c.max_iter, es = c.es;
     hipStream_t s = c.s;
     const StreamWs w = stream_ws(g, B, max_iter, c.work);
-    StreamArgs S{g->chk_ptr, g->ev, g->var_ptr, g->var_edge, g->M, g->N, g->E, B, w.msg, w.llrT, w.bitsT, w.done,
-                 w.iters, w.ctl, w.invalid, c.alpha, es, g->ext_var};
+    const StreamArgs S =
+        make_stream_args(g, B, c.alpha, es, w.msg, w.llrT, w.bitsT, w.done, w.iters, w.ctl, w.invalid, g->ext_var);
     LDPC_HIP(hipMemsetAsync(w.done, 0, (size_t)B, s));
     LDPC_HIP(hipMemsetAsync(w.ctl, 0, 64, s));
     LDPC_HIP(hipMemsetAsync(w.invalid, 0, (size_t)max_iter * 4, s));
-    const dim3 tgrid((unsigned)((B + 63) / 64), (unsigned)((g->N + 63) / 64));
-    hipLaunchKernelGGL(stream_transpose_llr_kernel, tgrid, dim3(256), 0, s, c.llr, B, g->N, w.llrT);
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    launch_stream_transpose(c.llr, B, g->N, w.llrT, s);
     for (int it = 0; it < max_iter; ++it) {
         if (it == 0)  // v2c = LLR (traditional_decoders.py:199-202) read in place of an init pass
             launch_stream_check<ALGO, true>(g, S, B, s);
@@ -398,14 +373,13 @@ int run_stream(const FloodCall &c) {
             launch_stream_check<ALGO>(g, S, B, s);
         launch_stream_var(g, S, B, it < max_iter - 1 ? 1 : 0, s);
         if (es != LDPC_ES_OFF) {
-            hipLaunchKernelGGL(stream_syndrome_kernel, blocks(B), dim3(256), 0, s, S, it);
+            launch_stream_syndrome(S, it, s);
             if (es == LDPC_ES_BATCH) hipLaunchKernelGGL(stream_batch_step_kernel, dim3(1), dim3(1), 0, s, S, it);
         }
         LDPC_CHECK_LAUNCH("stream iteration");
     }
     const bool want = c.counters || c.batch_iters;
-    hipLaunchKernelGGL(stream_emit_kernel, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, S, max_iter, c.out_dtype,
-                       c.bits, c.iters, want ? w.partials : nullptr);
+    launch_stream_emit(S, max_iter, c.out_dtype, c.bits, c.iters, want ? w.partials : nullptr, s);
     LDPC_CHECK_LAUNCH("stream emit");
     if (!want) return LDPC_OK;
     // batch_iters: ES off was set before the launch; otherwise the largest per-frame count
@@ -413,42 +387,20 @@ int run_stream(const FloodCall &c) {
                                nullptr, s);
 }
 
-// CustomMinSum workspace: the streaming arrays (msg, llrT) + probsT [N][B]
-int64_t custom_ws_bytes_(const ldpc_graph *g, int64_t B) {
-    return (int64_t)(align256((size_t)g->E * B * 4) + 2 * align256((size_t)g->N * B * 4));
-}
+// CustomMinSum workspace: the streaming arrays (msg, llrT) + probsT [N][B]; base == nullptr only sizes it
+struct CustomWs {
+    float *msg, *llrT, *probsT;
+    int64_t bytes;
+};
 
-int run_custom_minsum_(const ldpc_graph *g, const float *llr, int64_t B, int iterations, float *probs, void *work,
-                      hipStream_t s) {
-    char *base = static_cast<char *>(work);
-    StreamArgs S{};
-    S.chk_ptr = g->chk_ptr; S.ev = g->ev; S.var_ptr = g->var_ptr; S.var_edge = g->var_edge;
-    S.M = g->M; S.N = g->N; S.E = g->E; S.B = B;
-    S.msg = reinterpret_cast<float *>(base);
-    S.llrT = reinterpret_cast<float *>(base + align256((size_t)g->E * B * 4));
-    float *probsT = reinterpret_cast<float *>(base + align256((size_t)g->E * B * 4) + align256((size_t)g->N * B * 4));
-    S.alpha = 1.0f;
-    S.es = LDPC_ES_OFF;
-    // c2v = 0 at the start (MGD:1193): the first variable phase's FIRST form needs no zero-fill,
-    // zero iterations read the zeros directly
-    if (iterations == 0) LDPC_HIP(hipMemsetAsync(S.msg, 0, (size_t)g->E * B * 4, s));
-    hipLaunchKernelGGL(stream_transpose_llr_kernel, dim3((unsigned)((B + 63) / 64), (unsigned)((g->N + 63) / 64)),
-                       dim3(256), 0, s, llr, B, g->N, S.llrT);
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    for (int it = 0; it < iterations; ++it) {
-        if (it == 0)
-            launch_custom_var<true>(g, S, B, 0, s);
-        else
-            launch_custom_var<false>(g, S, B, 1, s);
-        launch_stream_check<LDPC_ALGO_MINSUM>(g, S, B, s);
-        LDPC_CHECK_LAUNCH("custom min-sum iteration");
-    }
-    hipLaunchKernelGGL(custom_output_kernel, blocks((int64_t)g->N * B), dim3(256), 0, s, S, probsT);
-    // (N, B) -> (B, N): the transpose kernel with the roles of the two extents swapped
-    hipLaunchKernelGGL(stream_transpose_llr_kernel, dim3((unsigned)((g->N + 63) / 64), (unsigned)((B + 63) / 64)),
-                       dim3(256), 0, s, probsT, (int64_t)g->N, (int)B, probs);
-    LDPC_CHECK_LAUNCH("custom min-sum output");
-    return LDPC_OK;
+CustomWs custom_ws(const ldpc_graph *g, int64_t B, void *base) {
+    CustomWs w{};
+    Arena a(base);
+    w.msg = a.take<float>(g->E * B * 4);
+    w.llrT = a.take<float>(g->N * B * 4);
+    w.probsT = a.take<float>(g->N * B * 4);
+    w.bytes = a.bytes;
+    return w;
 }
 
 }  // namespace
@@ -474,11 +426,32 @@ int run_stream_decode(int algo, const FloodCall &c) {
     return algo == LDPC_ALGO_MINSUM ? run_stream<LDPC_ALGO_MINSUM>(c) : run_stream<LDPC_ALGO_BP>(c);
 }
 
-int64_t custom_ws_bytes(const ldpc_graph *g, int64_t B) { return custom_ws_bytes_(g, B); }
+int64_t custom_ws_bytes(const ldpc_graph *g, int64_t B) { return custom_ws(g, B, nullptr).bytes; }
 
 int run_custom_minsum(const ldpc_graph *g, const float *llr, int64_t B, int iterations, float *probs, void *work,
                       hipStream_t s) {
-    return run_custom_minsum_(g, llr, B, iterations, probs, work, s);
+    const CustomWs w = custom_ws(g, B, work);
+    // alpha = 1, no stop, and no ext_var: the hybrid's check phase updates every edge
+    const StreamArgs S = make_stream_args(g, B, 1.0f, LDPC_ES_OFF, w.msg, w.llrT, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr, nullptr);
+    // c2v = 0 at the start (MGD:1193): the first variable phase's FIRST form needs no zero-fill,
+    // zero iterations read the zeros directly
+    if (iterations == 0) LDPC_HIP(hipMemsetAsync(S.msg, 0, (size_t)g->E * B * 4, s));
+    launch_stream_transpose(llr, B, g->N, S.llrT, s);
+    for (int it = 0; it < iterations; ++it) {
+        if (it == 0)
+            launch_custom_var<true>(g, S, B, 0, s);
+        else
+            launch_custom_var<false>(g, S, B, 1, s);
+        launch_stream_check<LDPC_ALGO_MINSUM>(g, S, B, s);
+        LDPC_CHECK_LAUNCH("custom min-sum iteration");
+    }
+    hipLaunchKernelGGL(custom_output_kernel, dim3((unsigned)(((int64_t)g->N * B + 255) / 256)), dim3(256), 0, s, S,
+                       w.probsT);
+    // (N, B) -> (B, N): the transpose kernel with the roles of the two extents swapped
+    launch_stream_transpose(w.probsT, g->N, (int)B, probs, s);
+    LDPC_CHECK_LAUNCH("custom min-sum output");
+    return LDPC_OK;
 }
 
 }  // namespace ldpc

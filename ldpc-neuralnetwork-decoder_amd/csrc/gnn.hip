@@ -1668,7 +1668,7 @@ struct Ws {
 Ws carve(const ldpc_gnn_plan *p, int H, int N, int64_t B, int layers, void *base, bool train = false,
          bool hybrid = false) {
     Ws w{};
-    GnnArena a(base);
+    Arena a(base);
     const int64_t es = 4;  // bytes per stored feature (fp32 path)
     const bool wide = wide_on(p, H) && !train;  // the last layer's rows are stored too (its head reads them)
     const int64_t x = B * p->E * H * es, mv = B * (int64_t)p->Gv * H * es, mc = B * (int64_t)p->Gc * H * es;

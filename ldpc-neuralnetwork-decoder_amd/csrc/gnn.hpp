@@ -110,21 +110,6 @@ __host__ __device__ inline GnnLayerWeights<P> gnn_layer_weights(P blob, int H, i
     return w;
 }
 
-// Workspace arena: a call's buffers lie in one caller allocation in the order they are taken, each
-// size rounded up to `align` bytes, so a buffer that is left out or taken with 0 bytes moves nothing
-// but what follows it.  base may be null (sizing): every pointer is then null and bytes still counts.
-struct GnnArena {
-    char *base;
-    int64_t bytes = 0;
-    explicit GnnArena(void *b) : base(static_cast<char *>(b)) {}
-    template <typename T>
-    T *take(int64_t n, int64_t align = 256) {
-        T *q = base ? reinterpret_cast<T *>(base + bytes) : nullptr;
-        bytes += (n + align - 1) / align * align;
-        return q;
-    }
-};
-
 // The current device's compute-unit count, queried once per process (gnn.hip)
 int gnn_num_cus(int *cus);
 

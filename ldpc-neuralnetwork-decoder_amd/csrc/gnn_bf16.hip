@@ -702,7 +702,7 @@ struct Bf16Ws {
 // The bf16 forward's buffers, taken in the order they lie in the workspace
 Bf16Ws carve_bf16(const ldpc_gnn_plan *p, int N, int64_t B, int T, int L, void *base) {
     Bf16Ws w;
-    GnnArena a(base);
+    Arena a(base);
     const int64_t memb = (int64_t)L * (p->Gv + p->Gc) * H * 4, x = B * p->E * H * 2;
     const int64_t nslot = (int64_t)p->n_ctiles * 32;
     w.kd = a.take<float>(L * kd_floats(T) * 4);

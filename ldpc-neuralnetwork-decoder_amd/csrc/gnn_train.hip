@@ -1662,7 +1662,7 @@ struct TrainWs {
 TrainWs carve_train(const ldpc_gnn_plan *p, int H, int N, int64_t B, void *base) {
     const int64_t reh = B * p->E * H, mv = B * p->Gv * H, mc = B * p->Gc * H, nz = B * N;  // floats
     TrainWs w;
-    GnnArena a(base);
+    Arena a(base);
     auto take = [&](int64_t n) { return a.take<float>(n * 4); };
     w.Mv = take(mv);
     w.Mc = take(mc);

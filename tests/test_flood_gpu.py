@@ -436,3 +436,96 @@ def test_cfg3_full_batch_with_errors_every_frame_vs_oracle(cuda, oracle_mod, H32
     else:
         assert (got != ref).mean() <= 1e-4, int((got != ref).sum())
     assert cnt.tolist() == [int(got.sum()), int((got.sum(1) > 0).sum()), B, 10 * B]
+
+
+# ---------------------------------------------------------------- streaming check rows of degree 11 .. 20
+def dense_row_H():
+    """The 24 x 50 non-QC graph of test_layered_stream_gpu (random_H(True)), restated: 48 columns of weight 3,
+    two appended degree-1 columns, and check 11 filled up to degree 16."""
+    rng = np.random.default_rng(2024)
+    H = np.zeros((24, 50), dtype=np.float32)
+    for j in range(48):
+        H[rng.choice(24, size=3, replace=False), j] = 1
+    H[5, 48] = 1
+    H[20, 49] = 1
+    H[11, rng.choice(48, size=14, replace=False)] = 1
+    return H
+
+
+ZERO_FRAMES, INF_FRAME, NAN_FRAME = (2, 40, 66), 5, 67
+
+
+def dense_row_llr(H):
+    """B = 70: one full wave and a partial one.  Frames 2, 40 and 66 (both waves) hold exact zeros in all,
+    every other and three of the dense row's variables, which takes the MinSumStats arm of the row rule;
+    frame 5 holds +-inf and frame 67 a NaN, both in the dense row."""
+    x = np.random.default_rng(9).normal(2.0, 1.5, size=(70, 50)).astype(np.float32)
+    row = np.flatnonzero(H[11])
+    x[2, row] = 0.0
+    x[40, row[::2]] = 0.0
+    x[66, row[:3]] = 0.0
+    x[INF_FRAME, row[1]] = np.inf
+    x[INF_FRAME, 7] = -np.inf
+    x[NAN_FRAME, row[4]] = np.nan
+    return x
+
+
+def flood_raw(g, algo, x, iters, alpha, es, cuda):
+    """ldpc_flood_decode with every output -> (bits, per-frame iterations, batch iterations, counters)"""
+    B = x.shape[0]
+    llr = torch.from_numpy(np.ascontiguousarray(x)).to(cuda)
+    bits = torch.empty((B, g.N), dtype=torch.uint8, device=cuda)
+    fi = torch.full((B,), -1, dtype=torch.int32, device=cuda)
+    bi = torch.zeros(1, dtype=torch.int32, device=cuda)
+    cnt = torch.zeros(4, dtype=torch.int64, device=cuda)
+    wsb = N.check(N.lib().ldpc_flood_workspace_size(g.handle, B, iters, es))
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=cuda)
+    N.check(N.lib().ldpc_flood_decode(g.handle, algo, N.ptr(llr), B, iters, alpha, es, N.LDPC_OUT_U8, N.ptr(bits),
+                                      N.ptr(fi), N.ptr(bi), N.ptr(cnt), N.ptr(ws), wsb, N.stream_ptr(cuda)))
+    torch.cuda.synchronize()
+    return bits.cpu().numpy(), fi.cpu().numpy(), int(bi.item()), cnt.cpu().numpy().tolist()
+
+
+@pytest.mark.parametrize("algo", ["minsum", "bp"])
+def test_streaming_dense_row_vs_oracle(cuda, oracle_mod, monkeypatch, algo):
+    """The flooding streaming check kernels past degree 10, which no BG2 lifting reaches: a check row of
+    degree 16 (and two of degree 11) on a small non-QC graph forced onto the streaming kernels, 3 iterations
+    (the first reads the LLRs, the others the messages), stop off, per frame and batch-global.
+    Min-sum: bits, per-frame and batch iteration counts and counters equal the oracle's exactly, zeros,
+    +-inf and NaN included.  BP: the per-variable rule of bp_rule.py as test_flood_bp_gpu applies it."""
+    from test_flood_bp_gpu import BATCH, FRAME, OFF, Code, check_path
+    monkeypatch.setenv("LDPC_FLOOD_STREAM", "1")
+    H = dense_row_H()
+    deg = H.sum(1).astype(int)
+    assert deg[11] == 16 and sorted(deg)[-3:] == [11, 11, 16] and (H.sum(0)[48:] == 1).all()
+    x = dense_row_llr(H)
+    special = list(ZERO_FRAMES) + [INF_FRAME, NAN_FRAME]
+    if algo == "bp":
+        code = Code(torch.from_numpy(H), oracle_mod, cuda)
+        assert code.g.max_dc == 16
+        r = code.rule("dense", x, 3)
+        r.check_floor([f for f in range(70) if f not in special])
+        assert np.isnan(r.a[0][:, NAN_FRAME]).any() and not r.clean[NAN_FRAME]
+        check_path(code, "dense", range(70), cuda, "streaming dense row", modes=(OFF, FRAME, BATCH), floor=False)
+        return
+    g = MinSumScaledDecoder(torch.from_numpy(H), 3).graph(cuda)
+    assert g.max_dc == 16 and g.Z == 1
+    og = oracle_mod.Graph(H)
+    early = None
+    for es in (N.LDPC_ES_OFF, N.LDPC_ES_FRAME, N.LDPC_ES_BATCH):
+        for iters in (1, 3):
+            rb, _, rn, ri = oracle_mod.flood_decode(og, x, "minsum", iters, 0.75, es)
+            bits, fi, bi, cnt = flood_raw(g, N.LDPC_ALGO_MINSUM, x, iters, 0.75, es, cuda)
+            assert np.array_equal(bits, rb), (es, iters)
+            assert np.array_equal(fi, ri), (es, iters)
+            assert bi == (int(ri.max()) if es == N.LDPC_ES_FRAME else rn), (es, iters)
+            assert cnt == [int(rb.sum()), int((rb.sum(1) > 0).sum()), 70, int(ri.sum())], (es, iters)
+        if es == N.LDPC_ES_FRAME:
+            assert set(np.unique(ri).tolist()) == {1, 2, 3}  # frames freeze at every iteration
+            early = np.flatnonzero(ri <= 2)
+    # the NaN frame is never valid, so the whole batch never stops: the frames valid by iteration 2 do
+    y = x[early]
+    rb, _, rn, ri = oracle_mod.flood_decode(og, y, "minsum", 3, 0.75, 1)
+    bits, fi, bi, cnt = flood_raw(g, N.LDPC_ALGO_MINSUM, y, 3, 0.75, N.LDPC_ES_BATCH, cuda)
+    assert rn == 2 and bi == 2 and np.array_equal(fi, ri) and np.array_equal(bits, rb)
+    assert cnt == [int(rb.sum()), int((rb.sum(1) > 0).sum()), len(y), int(ri.sum())]
