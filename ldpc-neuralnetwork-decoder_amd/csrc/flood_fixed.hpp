@@ -12,6 +12,8 @@
 //   msg[]   the messages of the wave's register edges (reg_edges() further down): edges whose
 //           check lane and variable lane are the same lane of this wave, so the message never
 //           leaves its VGPR -- no slot traffic, no rotation
+//   rmsg[]  the messages of the wave's rotated edges (further down): the wave's own edges with a
+//           shift, moved between their two lanes by one ds_swizzle_b32 -- no slot traffic either
 // so the iteration touches no global memory and computes no addresses: every message is a
 // ds_read at rot[s] + slot*256 (immediate offsets) and a ds_write_addtid at slot*256.  Both
 // phases are software-pipelined: the next row's / column's LDS reads are issued before the
@@ -78,9 +80,36 @@ constexpr int reg_edge_cap() {
     return BAIL ? kAllRegEdges : (ES == LDPC_ES_OFF ? LDPC_SLOW_REG_EDGES_OFF : LDPC_SLOW_REG_EDGES);
 }
 
+// Rotated edges (RE_ROW_ROT / RE_COL_ROT / RE_NROT): a slot edge outside msg[] whose row and column
+// are on one wave, with a normalised shift s != 0.  The wave produces and consumes the message
+// itself, so it moves between the check lane and the variable lane by one cross-lane rotation
+// inside the Z-lane segment (seg_rotate, at the producer) into rmsg[], instead of a slot store and
+// a rotated read: per edge and phase one LDS instruction that sends one VGPR to the LDS unit, not
+// two that send a data and an address VGPR.  That traffic, not the instruction count, is what the
+// phases' time follows (the same edges through ds_bpermute_b32, data + address,
+// gained nothing).  The slot stays allocated and unused, as a register edge's does.
+// An instance keeps at most this many over its four waves, handed out wave by wave, the wave with
+// the most slot edges in its columns first (the longest variable phase).  The exact-update
+// instance without early stop is at its 128 VGPRs already: none.
+#ifndef LDPC_ROT_EDGES
+#define LDPC_ROT_EDGES (1 << 20)
+#endif
+#ifndef LDPC_SLOW_ROT_EDGES
+#define LDPC_SLOW_ROT_EDGES (1 << 20)
+#endif
+#ifndef LDPC_SLOW_ROT_EDGES_OFF
+#define LDPC_SLOW_ROT_EDGES_OFF 0
+#endif
+template <int ES, bool BAIL>
+constexpr int rot_edge_cap() {
+    return BAIL ? LDPC_ROT_EDGES : (ES == LDPC_ES_OFF ? LDPC_SLOW_ROT_EDGES_OFF : LDPC_SLOW_ROT_EDGES);
+}
+
 // per-wave compile-time plan; CAP: the first CAP register edges of the wave's msg[] order are kept,
-// an edge past it is the shift-0 slot edge it still is (its slot stays allocated).  REG: reg_edges()
-template <class G, int WV, int CAP, bool REG>
+// an edge past it is the shift-0 slot edge it still is (its slot stays allocated).  RCAP: the
+// instance's rotated edges (above); an edge past the wave's share is the slot edge it still is.
+// REG: reg_edges()
+template <class G, int WV, int CAP, int RCAP, bool REG>
 struct FxPlan {
     // the wave's rows: the register-edge schedule's (RE_*) or the plain one's
     static constexpr int R0 = REG ? G::RE_CHK_PTR[WV] : G::CHK_PTR[WV];
@@ -93,6 +122,28 @@ struct FxPlan {
     static constexpr int col_shift(int j) { return REG ? G::RE_COL_SHIFT[j] : G::COL_SHIFT[j]; }
     static constexpr int row_reg(int e) { return REG && G::RE_ROW_REG[e] < CAP ? G::RE_ROW_REG[e] : -1; }
     static constexpr int col_reg(int j) { return REG && G::RE_COL_REG[j] < CAP ? G::RE_COL_REG[j] : -1; }
+    // the wave's share of the instance's RCAP rotated edges: what the waves with more slot edges
+    // in their columns (ties: the lower wave) leave of it
+    static constexpr int col_slot_edges(int w) {
+        int n = 0;
+        for (int i = G::VT_COL_PTR[w]; i < G::VT_COL_PTR[w + 1]; ++i)
+            for (int j = G::COL_PTR[G::VT_COLS[i]]; j < G::COL_PTR[G::VT_COLS[i] + 1]; ++j)
+                if (G::COL_SLOT[j] >= 0 && G::RE_COL_REG[j] < 0) ++n;
+        return n;
+    }
+    static constexpr int rot_share() {
+        if (!REG) return 0;
+        int left = RCAP;
+        for (int w = 0; w < G::W; ++w) {
+            const int a = col_slot_edges(w), b = col_slot_edges(WV);
+            if (a > b || (a == b && w < WV)) left -= G::RE_NROT[w];
+        }
+        return left < 0 ? 0 : (left < G::RE_NROT[WV] ? left : G::RE_NROT[WV]);
+    }
+    static constexpr int NROT = rot_share();
+    // the edge's index into rmsg[] (-1: not a rotated edge of this instance)
+    static constexpr int row_rot(int e) { return REG && G::RE_ROW_ROT[e] < NROT ? G::RE_ROW_ROT[e] : -1; }
+    static constexpr int col_rot(int j) { return REG && G::RE_COL_ROT[j] < NROT ? G::RE_COL_ROT[j] : -1; }
     // the wave's columns (LLRs in registers, init, shifts) and its variable tasks
     static constexpr int C0 = G::VT_COL_PTR[WV], NC = G::VT_COL_PTR[WV + 1] - C0;
     static constexpr int T0 = G::VT_PTR[WV], NT = G::VT_PTR[WV + 1] - T0;
@@ -112,6 +163,7 @@ struct FxPlan {
     static constexpr int inv_shift(int s) { return (G::Z - s) % G::Z; }
     // One rotation table per wave: the shifts of its columns (variable phase, lane t reads
     // position (t - s) mod Z) and the inverse shifts of its rows' slot edges (check phase).
+    // A rotated edge needs neither entry: its rotations are instruction constants (seg_rotate).
     static constexpr Tab make() {
         Tab t{};
         for (int i = 0; i < 64; ++i) t.shidx[i] = -1;
@@ -126,7 +178,7 @@ struct FxPlan {
             const int dv = G::COL_PTR[c + 1] - G::COL_PTR[c];
             if (dv > t.maxdv) t.maxdv = dv;
             for (int j = G::COL_PTR[c]; j < G::COL_PTR[c + 1]; ++j)
-                if (col_reg(j) < 0) use(col_shift(j));
+                if (col_reg(j) < 0 && col_rot(j) < 0) use(col_shift(j));
         }
         for (int i = 0; i < NR; ++i) {
             const int R = chk_row(i);
@@ -136,7 +188,7 @@ struct FxPlan {
             for (int e = G::ROW_PTR[R]; e < G::ROW_PTR[R + 1]; ++e) {
                 if (G::ROW_SLOT[e] < 0)
                     ++t.next;
-                else if (row_reg(e) < 0)
+                else if (row_reg(e) < 0 && row_rot(e) < 0)
                     use(inv_shift(row_shift(e)));
             }
         }
@@ -267,22 +319,34 @@ using DecOutFor = std::conditional_t<OUT < 0, NoOut, DecOut<G, OUT>>;
 
 // BAIL: the min-sum instance holds the fast check update only and leaves the decode when the sticky
 // flag is up (flood_drive, Body::kBail); otherwise check() branches to the exact form in the kernel.
-template <class G, int ALGO, int WV, bool BAIL, int CAP, bool REG>
+template <class G, int ALGO, int WV, bool BAIL, int CAP, int RCAP, bool REG>
 struct FixedBody {
     static_assert(!BAIL || ALGO == LDPC_ALGO_MINSUM, "only min-sum has a fast and an exact check update");
     static constexpr bool kBail = BAIL;
     static constexpr bool kPeel = true;  // decisions of the last iteration only are straight code behind the loop
-    using P = FxPlan<G, WV, CAP, REG>;
+    using P = FxPlan<G, WV, CAP, RCAP, REG>;
     static constexpr int ZM4 = 4 * G::Z - 1;
     static constexpr int NEXT = P::T.next > 0 ? P::T.next : 1;
     static constexpr int NCOL = P::NC > 0 ? P::NC : 1;
     static constexpr int NSH = P::T.nsh > 0 ? P::T.nsh : 1;
     static constexpr int MAXDC = P::T.maxdc, MAXDV = P::T.maxdv;
     static constexpr int NRG = P::NREG > 0 ? P::NREG : 1;
+    static constexpr int NRT = P::NROT > 0 ? P::NROT : 1;
     float ext[NEXT];
     float cllr[NCOL];
     uint32_t rot[NSH];  // absolute LDS byte addresses (lds_rd_abs)
     float msg[NRG];     // the messages of the wave's register edges: v2c after init / var, c2v after check
+    float rmsg[NRT];    // the messages of the wave's rotated edges, on the lane that reads them next:
+                        // v2c on the check lane after init / var, c2v on the variable lane after check
+
+
+    // a rotated edge's message (normalised shift S) moved to the lane that reads it next: variable
+    // lane t takes the c2v of check (t - S) mod Z, check lane k the v2c of variable (k + S) mod Z --
+    // the rotations the slot reads would have used
+    template <int S>
+    __device__ __forceinline__ float to_var_lane(float c2v) const { return seg_rotate<G::Z, S>(c2v); }
+    template <int S>
+    __device__ __forceinline__ float to_chk_lane(float v2c) const { return seg_rotate<G::Z, P::inv_shift(S)>(v2c); }
 
     __device__ __forceinline__ void init(Ctx &C, const Lane &L) {
         bool nan = false;
@@ -307,7 +371,8 @@ struct FixedBody {
                 rot[J] = opaque_vu(base + L.fz4 + ((L.k4 + (4 * G::Z - 4 * SH)) & ZM4));
         });
         // the first v2c of an edge is its column's LLR: variable-indexed, so stored own-lane (a
-        // register edge's variable lane is its check lane: the LLR goes into msg[], no store)
+        // register edge's variable lane is its check lane: the LLR goes into msg[], no store; a
+        // rotated edge's goes to its check lane)
         addtid_begin(C.lds);
         sfor<P::NC>([&](auto i) {
             constexpr int I = decltype(i)::value, COL = G::VT_COLS[P::C0 + I];
@@ -318,6 +383,8 @@ struct FixedBody {
                 constexpr int J = P0 + decltype(jj)::value;
                 if constexpr (P::col_reg(J) >= 0)
                     msg[P::col_reg(J)] = cllr[I];
+                else if constexpr (P::col_rot(J) >= 0)
+                    rmsg[P::col_rot(J)] = to_chk_lane<P::col_shift(J)>(cllr[I]);
                 else
                     lds_wr_tid<G::COL_SLOT[J] * 256>(cllr[I]);
             });
@@ -334,6 +401,8 @@ struct FixedBody {
             constexpr int E = decltype(e)::value, SL = G::ROW_SLOT[P0 + E];
             if constexpr (P::row_reg(P0 + E) >= 0)  // register edge: variable k's v2c is in this lane
                 v[E] = msg[P::row_reg(P0 + E)];
+            else if constexpr (P::row_rot(P0 + E) >= 0)  // rotated edge: var / init moved the v2c here
+                v[E] = rmsg[P::row_rot(P0 + E)];
             else if constexpr (SL >= 0)  // variable-indexed slot: row k's edge is at position (k + s) mod Z
                 v[E] = lds_rd_abs<SL * 256>(rot[P::T.shidx[P::inv_shift(P::row_shift(P0 + E))]]);
             else
@@ -350,6 +419,8 @@ struct FixedBody {
             constexpr int E = decltype(e)::value, SL = G::ROW_SLOT[P0 + E];
             if constexpr (P::row_reg(P0 + E) >= 0) {
                 msg[P::row_reg(P0 + E)] = o;  // register edge: the c2v stays in this lane
+            } else if constexpr (P::row_rot(P0 + E) >= 0) {
+                rmsg[P::row_rot(P0 + E)] = to_var_lane<P::row_shift(P0 + E)>(o);  // rotated edge: to its variable lane
             } else if constexpr (SL >= 0) {
                 lds_wr_tid<SL * 256>(o);  // ds_write_addtid_b32: the slot entry of a row is slot[lane]
             } else if constexpr (DEC) {
@@ -502,20 +573,25 @@ struct FixedBody {
     };
 
     // the c2v of the edge at index X of COL_*: from msg[] (register edge: check k's output is in
-    // this lane) or from its check-indexed slot, read rotated
+    // this lane), from rmsg[] (rotated edge: check moved it here) or from its check-indexed slot,
+    // read rotated
     template <int X>
     __device__ __forceinline__ float c2v_in() const {
         if constexpr (P::col_reg(X) >= 0)
             return msg[P::col_reg(X)];
+        else if constexpr (P::col_rot(X) >= 0)
+            return rmsg[P::col_rot(X)];
         else
             return lds_rd_abs<G::COL_SLOT[X] * 256>(rot[P::T.shidx[P::col_shift(X)]]);
     }
-    // the v2c of that edge: into msg[], or own-lane into its slot, which turns variable-indexed
+    // the v2c of that edge: into msg[], to its check lane's rmsg[], or own-lane into its slot, which turns variable-indexed
     // (ds_write_addtid_b32; every read of the slot was issued by load_task, before this store)
     template <int X>
     __device__ __forceinline__ void v2c_out(float o) {
         if constexpr (P::col_reg(X) >= 0)
             msg[P::col_reg(X)] = o;
+        else if constexpr (P::col_rot(X) >= 0)
+            rmsg[P::col_rot(X)] = to_chk_lane<P::col_shift(X)>(o);
         else
             lds_wr_tid<G::COL_SLOT[X] * 256>(o);
     }
@@ -699,7 +775,7 @@ __global__ __launch_bounds__(256, ES == LDPC_ES_OFF ? 4 : 3) void flood_fixed_ke
     init_ctx(C, Tc, lds, alpha, out_dtype, bits);
     if constexpr (BAIL) C.redo = redo;
     fx_by_wave<G>(__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), [&](auto wv) {
-        FixedBody<G, ALGO, decltype(wv)::value, BAIL, reg_edge_cap<ES, BAIL>(), reg_edges(ALGO)> body;
+        FixedBody<G, ALGO, decltype(wv)::value, BAIL, reg_edge_cap<ES, BAIL>(), rot_edge_cap<ES, BAIL>(), reg_edges(ALGO)> body;
         flood_drive<ES>(body, C, L, B, max_iter, O, W);
 #ifdef LDPC_TIMELINE
         if constexpr (ES == LDPC_ES_OFF) tl_bracket(O.timeline, decltype(wv)::value, t_in);

@@ -315,6 +315,22 @@ def gen(name, base, z, reg_edges=True, cap=None, report=None):
         s += arr("RE_NREG", [len(x) for x in reg])
         s += arr("RE_CHK_PTR", rp)
         s += arr("RE_CHK_ROWS", rl)
+        # rotated edges: a slot edge outside msg[] whose row and column are on the same wave but
+        # whose normalised shift is not 0.  Producer and consumer are the same wave, so the message
+        # can move between its check lane and its variable lane by one cross-lane rotation inside
+        # the Z-lane segment instead of a slot store and a rotated read (flood_fixed.hpp rmsg[]).
+        # Per edge the index into the wave's rmsg[] (-1: none), dense per wave in row order.
+        rowwave = {r: w for w in range(W) for r in rchk[w]}
+        colwave = {c: w for w in range(W) for t in vt[w] for c in t if c >= 0}
+        rot = [[i for i, b in enumerate(blocks) if slot[i] >= 0 and ridx[i] < 0 and rshift[i] != 0
+                and rowwave[b[0]] == w and colwave[b[1]] == w] for w in range(W)]
+        tidx = [-1] * len(blocks)
+        for w in range(W):
+            for x, i in enumerate(rot[w]):
+                tidx[i] = x
+        s += arr("RE_ROW_ROT", tidx)
+        s += arr("RE_COL_ROT", [tidx[i] for c in range(nb) for i in col_blocks[c]])
+        s += arr("RE_NROT", [len(x) for x in rot])
         if report is not None:
             c = dict(zip(rows, rcost))
             report[name] = dict(info, rho=rho, nreg=[len(x) for x in reg], rows=rchk,
@@ -363,10 +379,15 @@ def var_task_ops(DA, DB):
 
 
 def var_task_cost(DA, DB):
-    """Cycles of a variable task inside the running kernel: least squares over the measured phase
-    times of both schedules (tools/flood_timeline.py on the timeline builds, profiles/r04_flood_timeline_*):
-    8.2 per v_pk_add_f32 (its dependent chains issue slower than the 2.6-cycle ubench rate), 4.85
-    per v_add_f32, 18.1 per LDS read or write, 33.6 per task."""
+    """Modelled cycles of a variable task: the r04 least-squares fit over the phase times of the
+    schedules of that time (profiles/r04_flood_timeline_*): 8.2 per v_pk_add_f32, 4.85 per
+    v_add_f32, 18.1 per LDS read or write, 33.6 per task.  It only orders the schedules the search
+    compares and it pins the committed one (VT_*, RE_NREG); it is NOT the kernel's cost any more.
+    The fit predates own-lane stores, register edges and direct rows: measured on the kernel as it
+    is the four waves' variable phases are 2 327 / 2 666 / 2 161 /
+    2 612 cycles where this model says 2 525 / 2 520 / 2 518 / 2 385, a wave's time follows what its
+    LDS instructions send to the LDS unit (address and data VGPRs, shared by the CU's 16 waves), and
+    the scalar adds of a lone long column are nearly free."""
     pk, sc, rd, wr, apps = var_task_ops(DA, DB)
     return 8.21 * pk + 4.85 * sc + 18.12 * (rd + wr) + 33.6
 

@@ -61,9 +61,20 @@ def outside_loop(t, per, max_iter):
     def stat(a):
         return {"mean": round(float(np.mean(a)), 1), "median": round(float(np.median(a)), 1)} if len(a) else None
 
+    # placement: HW_ID[5:4] is the SIMD a wave ran on.  Per workgroup the SIMDs of its waves 0 .. 3,
+    # counted over the recorded workgroups, and how often all four waves share the workgroup's CU
+    simd = (where >> 4) & 3
+    tuples, counts = np.unique(simd, axis=0, return_counts=True)
+    order = np.argsort(-counts)[:8]
+    wave_cu = ((where >> 32) & 0xF) << 8 | ((where >> 8) & 0xFF)
+    placement = {"simd_of_waves_0_to_3": {"".join(str(int(x)) for x in tuples[i]): int(counts[i]) for i in order},
+                 "one_wave_per_simd": int((np.sort(simd, axis=1) == np.arange(4)).all(axis=1).sum()),
+                 "waves_on_one_cu": int((wave_cu == wave_cu[:, :1]).all(axis=1).sum())}
+
     return {
         "groups": int(len(e0)),
         "cus_seen": int(len(np.unique(cu))),
+        "placement": placement,
         "prologue": stat(pro), "loop": stat(loop), "epilogue": stat(epi), "lifetime": stat(life),
         "dead_share": round(float(np.mean(pro + epi) / np.mean(life)), 4),
         # the same for the workgroups that entered a freed slot (the first generation loads its
