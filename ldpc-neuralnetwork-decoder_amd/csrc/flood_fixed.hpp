@@ -105,30 +105,66 @@ constexpr int rot_edge_cap() {
     return BAIL ? LDPC_ROT_EDGES : (ES == LDPC_ES_OFF ? LDPC_SLOW_ROT_EDGES_OFF : LDPC_SLOW_ROT_EDGES);
 }
 
+// The joint schedule (gen/fixed_codes.hpp RE_J_*, tools/gen_fixed_codes.py joint_schedule): rows and
+// columns placed on the waves together so that the LDS operands of the heaviest wave of each phase
+// -- what an iteration's time follows -- are fewest: more edges have both
+// ends on one wave and fewer cross waves.  Checks are anonymous and everything that crosses kernels
+// (ballot words, candidates, decisions, the redo list) is per variable, so every instance picks its
+// family on its own: an instance reads the joint one where it fits its register budget without
+// scratch (the r18 register table), the others and BP keep the schedule they had.
+// LDPC_JOINT_MASK: bit 0 the BAIL instance without early stop (the flagship), bit 1 BAIL with the
+// per-frame stop, bit 2 the exact-update instance without early stop, bit 3 the other exact-update
+// instances (per-frame and batch stop, P1, P2); A/B builds set other masks.
+#ifndef LDPC_JOINT_MASK
+#define LDPC_JOINT_MASK 11
+#endif
+template <class G, int ALGO, int ES, bool BAIL>
+constexpr bool joint_family() {
+    if (!reg_edges(ALGO)) return false;
+    const int bit = BAIL ? (ES == LDPC_ES_OFF ? 0 : 1) : (ES == LDPC_ES_OFF ? 2 : 3);
+    return (LDPC_JOINT_MASK >> bit) & 1;
+}
+
 // per-wave compile-time plan; CAP: the first CAP register edges of the wave's msg[] order are kept,
 // an edge past it is the shift-0 slot edge it still is (its slot stays allocated).  RCAP: the
 // instance's rotated edges (above); an edge past the wave's share is the slot edge it still is.
-// REG: reg_edges()
-template <class G, int WV, int CAP, int RCAP, bool REG>
+// REG: reg_edges().  JOINT: the instance reads the joint schedule (RE_J_*, joint_family() below):
+// rows, shifts, register and rotated edges, columns and tasks all come from that family.
+template <class G, int WV, int CAP, int RCAP, bool REG, bool JOINT>
 struct FxPlan {
-    // the wave's rows: the register-edge schedule's (RE_*) or the plain one's
-    static constexpr int R0 = REG ? G::RE_CHK_PTR[WV] : G::CHK_PTR[WV];
-    static constexpr int NR = (REG ? G::RE_CHK_PTR[WV + 1] : G::CHK_PTR[WV + 1]) - R0;
-    static constexpr int NREG = !REG ? 0 : (G::RE_NREG[WV] < CAP ? G::RE_NREG[WV] : CAP);
-    static constexpr int chk_row(int i) { return REG ? G::RE_CHK_ROWS[R0 + i] : G::CHK_ROWS[R0 + i]; }
+    static_assert(REG || !JOINT, "the joint schedule is a register-edge schedule");
+    // the family's arrays: the joint schedule's, the register-edge schedule's or the plain one's
+    static constexpr int chk_ptr(int w) { return JOINT ? G::RE_J_CHK_PTR[w] : (REG ? G::RE_CHK_PTR[w] : G::CHK_PTR[w]); }
+    static constexpr int chk_rows(int x) { return JOINT ? G::RE_J_CHK_ROWS[x] : (REG ? G::RE_CHK_ROWS[x] : G::CHK_ROWS[x]); }
+    static constexpr int nreg(int w) { return JOINT ? G::RE_J_NREG[w] : G::RE_NREG[w]; }
+    static constexpr int nrot(int w) { return JOINT ? G::RE_J_NROT[w] : G::RE_NROT[w]; }
+    static constexpr int row_reg_all(int e) { return JOINT ? G::RE_J_ROW_REG[e] : G::RE_ROW_REG[e]; }
+    static constexpr int col_reg_all(int j) { return JOINT ? G::RE_J_COL_REG[j] : G::RE_COL_REG[j]; }
+    static constexpr int row_rot_all(int e) { return JOINT ? G::RE_J_ROW_ROT[e] : G::RE_ROW_ROT[e]; }
+    static constexpr int col_rot_all(int j) { return JOINT ? G::RE_J_COL_ROT[j] : G::RE_COL_ROT[j]; }
+    static constexpr int vt_col_ptr(int w) { return JOINT ? G::RE_J_VT_COL_PTR[w] : G::VT_COL_PTR[w]; }
+    static constexpr int vt_cols(int x) { return JOINT ? G::RE_J_VT_COLS[x] : G::VT_COLS[x]; }
+    static constexpr int vt_ptr(int w) { return JOINT ? G::RE_J_VT_PTR[w] : G::VT_PTR[w]; }
+    static constexpr int vt_a(int x) { return JOINT ? G::RE_J_VT_A[x] : G::VT_A[x]; }
+    static constexpr int vt_b(int x) { return JOINT ? G::RE_J_VT_B[x] : G::VT_B[x]; }
+    // the wave's rows
+    static constexpr int R0 = chk_ptr(WV);
+    static constexpr int NR = chk_ptr(WV + 1) - R0;
+    static constexpr int NREG = !REG ? 0 : (nreg(WV) < CAP ? nreg(WV) : CAP);
+    static constexpr int chk_row(int i) { return chk_rows(R0 + i); }
     // by edge index in row order (ROW_*) / in column order (COL_*): the (normalised) shift, and the
     // edge's index into msg[] (-1: the message lives in its LDS slot)
-    static constexpr int row_shift(int e) { return REG ? G::RE_ROW_SHIFT[e] : G::ROW_SHIFT[e]; }
-    static constexpr int col_shift(int j) { return REG ? G::RE_COL_SHIFT[j] : G::COL_SHIFT[j]; }
-    static constexpr int row_reg(int e) { return REG && G::RE_ROW_REG[e] < CAP ? G::RE_ROW_REG[e] : -1; }
-    static constexpr int col_reg(int j) { return REG && G::RE_COL_REG[j] < CAP ? G::RE_COL_REG[j] : -1; }
+    static constexpr int row_shift(int e) { return JOINT ? G::RE_J_ROW_SHIFT[e] : (REG ? G::RE_ROW_SHIFT[e] : G::ROW_SHIFT[e]); }
+    static constexpr int col_shift(int j) { return JOINT ? G::RE_J_COL_SHIFT[j] : (REG ? G::RE_COL_SHIFT[j] : G::COL_SHIFT[j]); }
+    static constexpr int row_reg(int e) { return REG && row_reg_all(e) < CAP ? row_reg_all(e) : -1; }
+    static constexpr int col_reg(int j) { return REG && col_reg_all(j) < CAP ? col_reg_all(j) : -1; }
     // the wave's share of the instance's RCAP rotated edges: what the waves with more slot edges
     // in their columns (ties: the lower wave) leave of it
     static constexpr int col_slot_edges(int w) {
         int n = 0;
-        for (int i = G::VT_COL_PTR[w]; i < G::VT_COL_PTR[w + 1]; ++i)
-            for (int j = G::COL_PTR[G::VT_COLS[i]]; j < G::COL_PTR[G::VT_COLS[i] + 1]; ++j)
-                if (G::COL_SLOT[j] >= 0 && G::RE_COL_REG[j] < 0) ++n;
+        for (int i = vt_col_ptr(w); i < vt_col_ptr(w + 1); ++i)
+            for (int j = G::COL_PTR[vt_cols(i)]; j < G::COL_PTR[vt_cols(i) + 1]; ++j)
+                if (G::COL_SLOT[j] >= 0 && col_reg_all(j) < 0) ++n;
         return n;
     }
     static constexpr int rot_share() {
@@ -136,20 +172,21 @@ struct FxPlan {
         int left = RCAP;
         for (int w = 0; w < G::W; ++w) {
             const int a = col_slot_edges(w), b = col_slot_edges(WV);
-            if (a > b || (a == b && w < WV)) left -= G::RE_NROT[w];
+            if (a > b || (a == b && w < WV)) left -= nrot(w);
         }
-        return left < 0 ? 0 : (left < G::RE_NROT[WV] ? left : G::RE_NROT[WV]);
+        return left < 0 ? 0 : (left < nrot(WV) ? left : nrot(WV));
     }
     static constexpr int NROT = rot_share();
     // the edge's index into rmsg[] (-1: not a rotated edge of this instance)
-    static constexpr int row_rot(int e) { return REG && G::RE_ROW_ROT[e] < NROT ? G::RE_ROW_ROT[e] : -1; }
-    static constexpr int col_rot(int j) { return REG && G::RE_COL_ROT[j] < NROT ? G::RE_COL_ROT[j] : -1; }
+    static constexpr int row_rot(int e) { return REG && row_rot_all(e) < NROT ? row_rot_all(e) : -1; }
+    static constexpr int col_rot(int j) { return REG && col_rot_all(j) < NROT ? col_rot_all(j) : -1; }
     // the wave's columns (LLRs in registers, init, shifts) and its variable tasks
-    static constexpr int C0 = G::VT_COL_PTR[WV], NC = G::VT_COL_PTR[WV + 1] - C0;
-    static constexpr int T0 = G::VT_PTR[WV], NT = G::VT_PTR[WV + 1] - T0;
+    static constexpr int C0 = vt_col_ptr(WV), NC = vt_col_ptr(WV + 1) - C0;
+    static constexpr int T0 = vt_ptr(WV), NT = vt_ptr(WV + 1) - T0;
+    static constexpr int col(int i) { return vt_cols(C0 + i); }
     static constexpr int col_index(int col) {
         for (int i = 0; i < NC; ++i)
-            if (G::VT_COLS[C0 + i] == col) return i;
+            if (vt_cols(C0 + i) == col) return i;
         return -1;
     }
     struct Tab {
@@ -174,7 +211,7 @@ struct FxPlan {
             }
         };
         for (int i = 0; i < NC; ++i) {
-            const int c = G::VT_COLS[C0 + i];
+            const int c = vt_cols(C0 + i);
             const int dv = G::COL_PTR[c + 1] - G::COL_PTR[c];
             if (dv > t.maxdv) t.maxdv = dv;
             for (int j = G::COL_PTR[c]; j < G::COL_PTR[c + 1]; ++j)
@@ -319,12 +356,12 @@ using DecOutFor = std::conditional_t<OUT < 0, NoOut, DecOut<G, OUT>>;
 
 // BAIL: the min-sum instance holds the fast check update only and leaves the decode when the sticky
 // flag is up (flood_drive, Body::kBail); otherwise check() branches to the exact form in the kernel.
-template <class G, int ALGO, int WV, bool BAIL, int CAP, int RCAP, bool REG>
+template <class G, int ALGO, int WV, bool BAIL, int CAP, int RCAP, bool REG, bool JOINT>
 struct FixedBody {
     static_assert(!BAIL || ALGO == LDPC_ALGO_MINSUM, "only min-sum has a fast and an exact check update");
     static constexpr bool kBail = BAIL;
     static constexpr bool kPeel = true;  // decisions of the last iteration only are straight code behind the loop
-    using P = FxPlan<G, WV, CAP, RCAP, REG>;
+    using P = FxPlan<G, WV, CAP, RCAP, REG, JOINT>;
     static constexpr int ZM4 = 4 * G::Z - 1;
     static constexpr int NEXT = P::T.next > 0 ? P::T.next : 1;
     static constexpr int NCOL = P::NC > 0 ? P::NC : 1;
@@ -333,7 +370,11 @@ struct FixedBody {
     static constexpr int NRG = P::NREG > 0 ? P::NREG : 1;
     static constexpr int NRT = P::NROT > 0 ? P::NROT : 1;
     float ext[NEXT];
-    float cllr[NCOL];
+    // one float past the wave's columns, never written: the compiler widens a pair task's load of
+    // cllr[IA] to two floats, and where that reached into rot[] and overlapped the next pair's load
+    // the arrays stayed in scratch memory.  Only the joint schedule's column lists meet that, so only
+    // its instances carry the float: the others' code stays what it was
+    float cllr[NCOL + (JOINT ? 1 : 0)];
     uint32_t rot[NSH];  // absolute LDS byte addresses (lds_rd_abs)
     float msg[NRG];     // the messages of the wave's register edges: v2c after init / var, c2v after check
     float rmsg[NRT];    // the messages of the wave's rotated edges, on the lane that reads them next:
@@ -375,7 +416,7 @@ struct FixedBody {
         // rotated edge's goes to its check lane)
         addtid_begin(C.lds);
         sfor<P::NC>([&](auto i) {
-            constexpr int I = decltype(i)::value, COL = G::VT_COLS[P::C0 + I];
+            constexpr int I = decltype(i)::value, COL = P::col(I);
             constexpr int P0 = G::COL_PTR[COL], DV = G::COL_PTR[COL + 1] - P0;
             cllr[I] = L.llr_at(COL * 4 * G::Z + L.k4);
             nan |= !(fabsf(cllr[I]) < INFINITY);
@@ -403,10 +444,12 @@ struct FixedBody {
                 v[E] = msg[P::row_reg(P0 + E)];
             else if constexpr (P::row_rot(P0 + E) >= 0)  // rotated edge: var / init moved the v2c here
                 v[E] = rmsg[P::row_rot(P0 + E)];
-            else if constexpr (SL >= 0)  // variable-indexed slot: row k's edge is at position (k + s) mod Z
+            else if constexpr (SL >= 0) {  // variable-indexed slot: row k's edge is at position (k + s) mod Z
+                static_assert(P::T.shidx[P::inv_shift(P::row_shift(P0 + E))] >= 0, "rot[] holds the rotation");
                 v[E] = lds_rd_abs<SL * 256>(rot[P::T.shidx[P::inv_shift(P::row_shift(P0 + E))]]);
-            else
+            } else {
                 v[E] = ext[P::ext_index(I, E)];
+            }
         });
     }
 
@@ -560,12 +603,13 @@ struct FixedBody {
     template <int TK>
     struct Task {
         static constexpr int X = P::T0 + TK;
-        static constexpr int CA = G::VT_A[X], CB = G::VT_B[X];
+        static constexpr int CA = P::vt_a(X), CB = P::vt_b(X);
         static constexpr int PA = G::COL_PTR[CA], DA = G::COL_PTR[CA + 1] - PA;
         static constexpr int PB = CB >= 0 ? G::COL_PTR[CB] : 0, DB = CB >= 0 ? G::COL_PTR[CB + 1] - PB : 0;
         static_assert(DB <= DA, "pair tasks: A is the longer column");
         static constexpr int IA = P::col_index(CA), IB = CB >= 0 ? P::col_index(CB) : 0;
         static constexpr int NMSG = DA + DB;
+        static_assert(IA >= 0 && IB >= 0, "a task's columns are columns of its wave");
     };
     struct TaskIn {
         f32x2 cp[MAXDV];  // J < DB: {c_A[J], c_B[J]}
@@ -581,8 +625,10 @@ struct FixedBody {
             return msg[P::col_reg(X)];
         else if constexpr (P::col_rot(X) >= 0)
             return rmsg[P::col_rot(X)];
-        else
+        else {
+            static_assert(P::T.shidx[P::col_shift(X)] >= 0, "rot[] holds the rotation");
             return lds_rd_abs<G::COL_SLOT[X] * 256>(rot[P::T.shidx[P::col_shift(X)]]);
+        }
     }
     // the v2c of that edge: into msg[], to its check lane's rmsg[], or own-lane into its slot, which turns variable-indexed
     // (ds_write_addtid_b32; every read of the slot was issued by load_task, before this store)
@@ -775,7 +821,7 @@ __global__ __launch_bounds__(256, ES == LDPC_ES_OFF ? 4 : 3) void flood_fixed_ke
     init_ctx(C, Tc, lds, alpha, out_dtype, bits);
     if constexpr (BAIL) C.redo = redo;
     fx_by_wave<G>(__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), [&](auto wv) {
-        FixedBody<G, ALGO, decltype(wv)::value, BAIL, reg_edge_cap<ES, BAIL>(), rot_edge_cap<ES, BAIL>(), reg_edges(ALGO)> body;
+        FixedBody<G, ALGO, decltype(wv)::value, BAIL, reg_edge_cap<ES, BAIL>(), rot_edge_cap<ES, BAIL>(), reg_edges(ALGO), joint_family<G, ALGO, ES, BAIL>()> body;
         flood_drive<ES>(body, C, L, B, max_iter, O, W);
 #ifdef LDPC_TIMELINE
         if constexpr (ES == LDPC_ES_OFF) tl_bracket(O.timeline, decltype(wv)::value, t_in);

@@ -31,6 +31,16 @@ REG_EDGE_CAP = 16
 # the read and the write of var_task_cost
 CHK_EDGE_LDS = 2.0
 VAR_EDGE_LDS = 18.12
+# The joint schedule (RE_J_* arrays, joint_schedule() below): at most this many kept messages
+# (msg[] + rmsg[]) per wave -- with it the flagship instance uses 127 of its 128 VGPRs, without
+# scratch (the r18 register table) -- and a column pair is formed only while the two
+# columns hold at most this many messages together (the committed VT_* pairs hold at most 30: a
+# task's accumulators are all live at once).
+JOINT_KEPT_CAP = 24
+JOINT_PAIR_MSGS = 30
+JOINT_STARTS = 4
+JOINT_WANDER = 25000
+JOINT_THRESHOLD = 400
 
 
 def load(path):
@@ -218,7 +228,330 @@ def reg_edge_schedule(blocks, z, mb, dv, row_ptr, rcost, sched, cap):
     return rho, [[r for r in range(mb) if wave[r] == w] for w in range(W)], reg, info
 
 
-def gen(name, base, z, reg_edges=True, cap=None, report=None):
+def operand_table(blocks, slot, rowwave, colwave, ridx, tidx):
+    """LDS operands per wave and iteration: what the wave's LDS instructions
+    send to the CU's LDS unit.  A slot edge sends 2 per phase (the read's address VGPR and the
+    ds_write_addtid_b32's data VGPR), a rotated edge 1 (the swizzle's data VGPR), a register edge
+    none; the check phase counts an edge on its row's wave, the variable phase on its column's."""
+    chk, var = [0] * W, [0] * W
+    for i, (r, c, _) in enumerate(blocks):
+        if slot[i] < 0:
+            continue
+        n = 0 if ridx[i] >= 0 else (1 if tidx[i] >= 0 else 2)
+        chk[rowwave[r]] += n
+        var[colwave[c]] += n
+    return chk, var
+
+
+def wave_tasks(cols, dv):
+    """The variable tasks of one wave's columns by the pairing rule of var_schedule: the columns
+    sorted by degree, every pattern of pairing neighbours in that order (a pair holds at most
+    JOINT_PAIR_MSGS messages), the least modelled cost wins (ties: the first pattern, lone columns
+    first).  Returns ([(A, B or -1)] sorted, the tasks' modelled VALU load)."""
+    cols = sorted(cols, key=lambda c: (-dv[c], c))
+    n = len(cols)
+
+    def pats(i):
+        if i >= n:
+            return [[]]
+        out = [[(cols[i], -1)] + p for p in pats(i + 1)]
+        if i + 1 < n and dv[cols[i]] + dv[cols[i + 1]] <= JOINT_PAIR_MSGS:
+            out += [[(cols[i], cols[i + 1])] + p for p in pats(i + 2)]
+        return out
+    best = None
+    for pat in pats(0):
+        cost = sum(var_task_cost(dv[a], dv[b] if b >= 0 else 0) for a, b in pat)
+        if best is None or cost < best[0] - 1e-9:
+            best = (cost, pat)
+    return sorted(best[1]), sum(var_task_valu(dv[a], dv[b] if b >= 0 else 0) for a, b in best[1])
+
+
+def var_task_valu(DA, DB):
+    """modelled VALU load of a variable task: var_task_ops's adds at var_task_cost's unit costs"""
+    pk, sc, _, _, _ = var_task_ops(DA, DB)
+    return 8.21 * pk + 4.85 * sc
+
+
+def joint_schedule(blocks, z, mb, nb, dv, slot, rcost, old_rowwave, old_colwave, cap):
+    """The joint schedule (RE_J_* arrays): block rows and slot-bearing columns are put on the waves
+    together, so that what the phases' time follows -- the LDS operands of operand_table -- is what
+    the search minimises, where var_schedule balances a cost fit and reg_edge_schedule then counts
+    shift-0 edges only.
+
+    Given the waves, rho_r turns the shift that most of row r's same-wave slot edges share into 0
+    (ties: the smallest offset): those edges are register edges, the row's other same-wave edges
+    rotated edges.  A wave keeps at most `cap` of them (msg[] + rmsg[]): past it the last rotated
+    edges in row order, then the last register edges, stay slot edges.
+
+    Key, smallest first: max over waves of the check operands + max of the variable operands; total
+    operands; the spread (max - min) of the modelled VALU loads of both phases (rcost; var_task_valu
+    over wave_tasks).  The modelled VALU load is a key, not a bound: with the heaviest wave of each
+    phase held to the committed schedule's excess over the mean (check 0.9 %, variable 13.9 %) the
+    same search ends at 108 / 410 operands (max + max / total) for BG2 Z=32 against the committed
+    115 / 420, without it at 98 / 380, and the phases' time follows the operands, not that load
+    (DESIGN.md 3.1, r17 and r18).
+    Starts: the committed schedule, then JOINT_STARTS - 1 shuffles from a fixed linear congruential
+    sequence; from each, wander() and then first-improvement passes over single moves of a row or a
+    column and swaps of two rows or two columns until none improves the key.  Between the starts'
+    results the number of rot[] entries of the four waves breaks a tie of the key.  Deterministic.
+    Returns a dict: rho, rowwave, colwave, reg / rot (edge indices per wave in row order), tasks."""
+    vcols = [c for c in range(nb) if dv[c] >= 2]
+    redges = [[(i, c, s) for i, (q, c, s) in enumerate(blocks) if q == r and slot[i] >= 0] for r in range(mb)]
+    rows_of = {c: sorted({r for r in range(mb) for _, cc, _ in redges[r] if cc == c}) for c in vcols}
+
+    def row_choice(r, w, cw):
+        """(rho, register edges, rotated edges) of row r on wave w, edge indices in row order"""
+        same = [(i, s) for i, c, s in redges[r] if cw[c] == w]
+        if not same:
+            return 0, [], []
+        cnt = {}
+        for _, s in same:
+            cnt[s] = cnt.get(s, 0) + 1
+        s0 = min(cnt, key=lambda s: (-cnt[s], (-s) % z))
+        return (-s0) % z, [i for i, s in same if s == s0], [i for i, s in same if s != s0]
+
+    def row_entry(r, w, cw):
+        _, reg, rot = row_choice(r, w, cw)
+        var = [0] * W
+        for _, c, _ in redges[r]:
+            if cw[c] != w:
+                var[cw[c]] += 2
+        var[w] += len(rot)
+        return 2 * (len(redges[r]) - len(reg) - len(rot)) + len(rot), var, len(reg), len(rot)
+
+    tasks_memo = {}
+
+    def var_valu(cw):
+        out = []
+        for w in range(W):
+            k = tuple(c for c in vcols if cw[c] == w)
+            if k not in tasks_memo:
+                tasks_memo[k] = wave_tasks(k, dv)[1] if k else 0.0
+            out.append(tasks_memo[k])
+        return out
+
+    # row costs in integer thousandths: sums kept up to date move by move stay exact
+    rc = [int(round(1000 * x)) for x in rcost]
+
+    def place(acc, r, w, tab, sign):
+        """add (sign = 1) or take away (-1) row r on wave w: acc = [chk, var, nreg, nrot, cv]"""
+        e = tab[r][w]
+        acc[0][w] += sign * e[0]
+        for q in range(W):
+            acc[1][q] += sign * e[1][q]
+        acc[2][w] += sign * e[2]
+        acc[3][w] += sign * e[3]
+        acc[4][w] += sign * rc[r]
+
+    def sums(rw, tab):
+        acc = [[0] * W for _ in range(5)]
+        for r in range(mb):
+            place(acc, r, rw[r], tab, 1)
+        return acc
+
+    def key_of(acc, vv):
+        chk, var, nreg, nrot, cv = acc
+        mc, mv, tot, sq = 0, 0, 0, 0
+        for w in range(W):  # past the cap: rotated edges first, then register edges, stay slot edges
+            d = nreg[w] + nrot[w] - cap
+            back = min(d, nrot[w]) + 2 * max(0, d - nrot[w]) if d > 0 else 0
+            c, v = chk[w] + back, var[w] + back
+            mc, mv, tot, sq = max(mc, c), max(mv, v), tot + c + v, sq + c * c + v * v
+        return (mc + mv, tot, round((max(cv) - min(cv)) / 1000 + max(vv) - min(vv), 6)), sq
+
+    def key(rw, cw, tab):
+        return key_of(sums(rw, tab), var_valu(cw))[0]
+
+    def table(cw, rows=None, tab=None):
+        tab = [None] * mb if tab is None else tab
+        for r in (range(mb) if rows is None else rows):
+            tab[r] = [row_entry(r, w, cw) for w in range(W)]
+        return tab
+
+    def descend(rw, cw):
+        tab = table(cw)
+        cur = key(rw, cw, tab)
+        improved = True
+        while improved:
+            improved = False
+            for r in range(mb):  # a row to another wave
+                for w in range(W):
+                    if w == rw[r]:
+                        continue
+                    keep, rw[r] = rw[r], w
+                    k = key(rw, cw, tab)
+                    if k < cur:
+                        cur, improved = k, True
+                    else:
+                        rw[r] = keep
+            for r in range(mb):  # two rows change places
+                for q in range(r + 1, mb):
+                    if rw[r] == rw[q]:
+                        continue
+                    rw[r], rw[q] = rw[q], rw[r]
+                    k = key(rw, cw, tab)
+                    if k < cur:
+                        cur, improved = k, True
+                    else:
+                        rw[r], rw[q] = rw[q], rw[r]
+            for c in vcols:  # a column to another wave
+                for w in range(W):
+                    if w == cw[c]:
+                        continue
+                    keep, cw[c] = cw[c], w
+                    saved = [tab[r] for r in rows_of[c]]
+                    table(cw, rows_of[c], tab)
+                    k = key(rw, cw, tab)
+                    if k < cur:
+                        cur, improved = k, True
+                    else:
+                        cw[c] = keep
+                        for r, e in zip(rows_of[c], saved):
+                            tab[r] = e
+            for x, c in enumerate(vcols):  # two columns change places
+                for d in vcols[x + 1:]:
+                    if cw[c] == cw[d]:
+                        continue
+                    touched = sorted(set(rows_of[c]) | set(rows_of[d]))
+                    saved = [tab[r] for r in touched]
+                    cw[c], cw[d] = cw[d], cw[c]
+                    table(cw, touched, tab)
+                    k = key(rw, cw, tab)
+                    if k < cur:
+                        cur, improved = k, True
+                    else:
+                        cw[c], cw[d] = cw[d], cw[c]
+                        for r, e in zip(touched, saved):
+                            tab[r] = e
+        return cur
+
+    def classify(rw, cw):
+        rho, reg, rot = [0] * mb, [[] for _ in range(W)], [[] for _ in range(W)]
+        for r in range(mb):
+            rho[r], a, b = row_choice(r, rw[r], cw)
+            reg[rw[r]] += a
+            rot[rw[r]] += b
+        for w in range(W):
+            rot[w] = rot[w][:max(0, cap - min(cap, len(reg[w])))]
+            reg[w] = reg[w][:cap]
+        return rho, reg, rot
+
+    def rotations(rw, cw):
+        rho, reg, rot = classify(rw, cw)
+        n = 0
+        for w in range(W):
+            kept = set(reg[w]) | set(rot[w])
+            s = set()
+            for i, (r, c, sh) in enumerate(blocks):
+                if slot[i] < 0 or i in kept:
+                    continue
+                if cw[c] == w:
+                    s.add((sh + rho[r]) % z)
+                if rw[r] == w:
+                    s.add((-(sh + rho[r])) % z)
+            n += len(s)
+        return n
+
+    state = [0x9E3779B97F4A7C15]
+
+    def rnd(n):
+        state[0] = (state[0] * 6364136223846793005 + 1442695040888963407) % (1 << 64)
+        return (state[0] >> 33) % n
+
+    def shuffled(items):
+        items = list(items)
+        for i in range(len(items) - 1, 0, -1):
+            j = rnd(i + 1)
+            items[i], items[j] = items[j], items[i]
+        return items
+
+    def wander(rw, cw):
+        """Threshold accepting before the descent: JOINT_WANDER random single moves and swaps, one
+        in eight on columns, each taken when the sum over waves and phases of the squared operands (a
+        smooth stand-in for max + max and total together) rises by no more than a threshold that
+        falls from JOINT_THRESHOLD to 0 (integers only).  Leaves the state with the best (max + max,
+        total) met in rw / cw."""
+        tab = table(cw)
+        acc, vv = sums(rw, tab), var_valu(cw)
+        k, cur = key_of(acc, vv)
+        best = (k[:2], list(rw), dict(cw))
+
+        def set_rows(rows, waves):
+            for r, w in zip(rows, waves):
+                place(acc, r, rw[r], tab, -1)
+                rw[r] = w
+                place(acc, r, w, tab, 1)
+
+        def set_cols(cols, waves):
+            touched = sorted({r for c in cols for r in rows_of[c]})
+            for r in touched:
+                place(acc, r, rw[r], tab, -1)
+            for c, w in zip(cols, waves):
+                cw[c] = w
+            table(cw, touched, tab)
+            for r in touched:
+                place(acc, r, rw[r], tab, 1)
+
+        for t in range(JOINT_WANDER):
+            thr = JOINT_THRESHOLD * (JOINT_WANDER - t) // JOINT_WANDER
+            kind = rnd(16)
+            if kind < 14:  # rows: a move (kind < 7) or a swap
+                r, q = rnd(mb), rnd(mb)
+                keep = (rw[r], rw[q])
+                new = (rnd(W), rw[q]) if kind < 7 else (rw[q], rw[r])
+                if new == keep or r == q:
+                    continue
+                set_rows((r, q), new)
+                k, sq = key_of(acc, vv)
+                if sq <= cur + thr:
+                    cur = sq
+                else:
+                    set_rows((r, q), keep)
+                    continue
+            else:  # columns: a move (kind 14) or a swap
+                c, d = vcols[rnd(len(vcols))], vcols[rnd(len(vcols))]
+                keep = (cw[c], cw[d])
+                new = (rnd(W), cw[d]) if kind == 14 else (cw[d], cw[c])
+                if new == keep or c == d:
+                    continue
+                set_cols((c, d), new)
+                keepv, vv = vv, var_valu(cw)
+                k, sq = key_of(acc, vv)
+                if sq <= cur + thr:
+                    cur = sq
+                else:
+                    set_cols((c, d), keep)
+                    vv = keepv
+                    continue
+            if k[:2] < best[0]:
+                best = (k[:2], list(rw), dict(cw))
+        rw[:] = best[1]
+        cw.update(best[2])
+
+    best = None
+    for start in range(JOINT_STARTS):
+        if start == 0:
+            rw, cw = list(old_rowwave), dict(old_colwave)
+        else:  # columns and rows dealt round the waves in a shuffled order
+            cw = {c: x % W for x, c in enumerate(shuffled(vcols))}
+            rw = [0] * mb
+            for x, r in enumerate(shuffled(range(mb))):
+                rw[r] = x % W
+        wander(rw, cw)
+        k = descend(rw, cw) + (rotations(rw, cw),)
+        if best is None or k < best[0]:
+            best = (k, list(rw), dict(cw))
+    _, rw, cw = best
+    rho, reg, rot = classify(rw, cw)
+    return {"rho": rho, "rowwave": rw, "colwave": cw, "reg": reg, "rot": rot, "key": best[0],
+            "tasks": [wave_tasks([c for c in vcols if cw[c] == w], dv)[0] if any(cw[c] == w for c in vcols) else []
+                      for w in range(W)]}
+
+
+_joint_memo = {}
+
+
+def gen(name, base, z, reg_edges=True, cap=None, report=None, joint_cap=None):
     mb, nb = len(base), len(base[0])
     blocks = [(r, c, base[r][c] % z) for r in range(mb) for c in range(nb) if base[r][c] >= 0]
     dv = [0] * nb
@@ -331,6 +664,53 @@ def gen(name, base, z, reg_edges=True, cap=None, report=None):
         s += arr("RE_ROW_ROT", tidx)
         s += arr("RE_COL_ROT", [tidx[i] for c in range(nb) for i in col_blocks[c]])
         s += arr("RE_NROT", [len(x) for x in rot])
+        # the joint schedule (joint_schedule): the same arrays again as RE_J_*, with columns and
+        # tasks of its own (RE_J_VT_*: the VT_* layout) and its LDS operands per wave.  An instance
+        # of the kernel reads one family or the other (flood_fixed.hpp FxPlan).
+        jcap = JOINT_KEPT_CAP if joint_cap is None else joint_cap
+        if (name, jcap) not in _joint_memo:
+            _joint_memo[(name, jcap)] = joint_schedule(blocks, z, mb, nb, dv, slot, rcost,
+                                                       [rowwave[r] for r in range(mb)], colwave, jcap)
+        j = _joint_memo[(name, jcap)]
+        jshift = [(b[2] + j["rho"][b[0]]) % z for b in blocks]
+        jreg, jrot = [-1] * len(blocks), [-1] * len(blocks)
+        for w in range(W):
+            for x, i in enumerate(j["reg"][w]):
+                jreg[i] = x
+            for x, i in enumerate(j["rot"][w]):
+                jrot[i] = x
+        jrp, jrl = flat([[r for r in range(mb) if j["rowwave"][r] == w] for w in range(W)])
+        jvp, jvl = flat([sorted(c for t in p for c in t if c >= 0) for p in j["tasks"]])
+        jtp, jtl = flat(j["tasks"])
+        ops_old = operand_table(blocks, slot, rowwave, colwave, ridx, tidx)
+        ops_new = operand_table(blocks, slot, j["rowwave"], j["colwave"], jreg, jrot)
+        s += f"    static constexpr int RE_J_CAP = {jcap};\n"
+        s += arr("RE_J_RHO", j["rho"])
+        s += arr("RE_J_ROW_SHIFT", jshift)
+        s += arr("RE_J_COL_SHIFT", [jshift[i] for c in range(nb) for i in col_blocks[c]])
+        s += arr("RE_J_ROW_REG", jreg)
+        s += arr("RE_J_COL_REG", [jreg[i] for c in range(nb) for i in col_blocks[c]])
+        s += arr("RE_J_NREG", [len(x) for x in j["reg"]])
+        s += arr("RE_J_CHK_PTR", jrp)
+        s += arr("RE_J_CHK_ROWS", jrl)
+        s += arr("RE_J_ROW_ROT", jrot)
+        s += arr("RE_J_COL_ROT", [jrot[i] for c in range(nb) for i in col_blocks[c]])
+        s += arr("RE_J_NROT", [len(x) for x in j["rot"]])
+        s += arr("RE_J_VT_COL_PTR", jvp)
+        s += arr("RE_J_VT_COLS", jvl)
+        s += arr("RE_J_VT_PTR", jtp)
+        s += arr("RE_J_VT_A", [t[0] for t in jtl])
+        s += arr("RE_J_VT_B", [t[1] for t in jtl])
+        s += arr("RE_J_OPS_CHK", ops_new[0])
+        s += arr("RE_J_OPS_VAR", ops_new[1])
+        if report is not None:
+            report[name + " LDS operands"] = {"old chk": ops_old[0], "old var": ops_old[1],
+                                              "old max+max, total": [max(ops_old[0]) + max(ops_old[1]), sum(ops_old[0]) + sum(ops_old[1])],
+                                              "joint chk": ops_new[0], "joint var": ops_new[1],
+                                              "joint max+max, total": [max(ops_new[0]) + max(ops_new[1]), sum(ops_new[0]) + sum(ops_new[1])],
+                                              "joint nreg": [len(x) for x in j["reg"]], "joint nrot": [len(x) for x in j["rot"]],
+                                              "joint columns": [sorted(c for c in j["colwave"] if j["colwave"][c] == w) for w in range(W)],
+                                              "joint key": list(j["key"])}
         if report is not None:
             c = dict(zip(rows, rcost))
             report[name] = dict(info, rho=rho, nreg=[len(x) for x in reg], rows=rchk,
@@ -423,13 +803,13 @@ def var_schedule(vcols, dv, w):
     return [sorted(p) for p in best[1]]
 
 
-def header_text(reg_edges=True, cap=None, report=None):
+def header_text(reg_edges=True, cap=None, report=None, joint_cap=None):
     """The header's text; reg_edges=False leaves the RE_* arrays out (the schedule before them)."""
     text = ("// GENERATED by tools/gen_fixed_codes.py from codes/NR_2_0_{4,32}.txt -- do not edit.\n"
             "// Compile-time flooding schedules for the two codes the reference ships (see that script).\n"
             "#pragma once\n\nnamespace ldpc {\nnamespace fixed {\n\n")
     for name, path, z in CODES:
-        text += gen(name, load(path), z, reg_edges, cap, report)
+        text += gen(name, load(path), z, reg_edges, cap, report, joint_cap)
     text += "}  // namespace fixed\n}  // namespace ldpc\n"
     return text
 
@@ -437,8 +817,10 @@ def header_text(reg_edges=True, cap=None, report=None):
 def main(out):
     # LDPC_REG_EDGE_CAP: a smaller cap for A/B builds (tools/build_variant.sh on a copy of the tree)
     cap = int(os.environ["LDPC_REG_EDGE_CAP"]) if os.environ.get("LDPC_REG_EDGE_CAP") else None
+    # LDPC_JOINT_CAP: another cap on the joint schedule's kept messages per wave (register budget)
+    jcap = int(os.environ["LDPC_JOINT_CAP"]) if os.environ.get("LDPC_JOINT_CAP") else None
     report = {}
-    text = header_text(True, cap, report)
+    text = header_text(True, cap, report, jcap)
     if os.environ.get("LDPC_GEN_REPORT"):
         for name, r in report.items():
             print(name, {k: ([round(x, 1) for x in v] if k in ("chk", "var", "chk_old", "var_old") else v)
